@@ -16,14 +16,20 @@ streams, the max-over-ranks timing and the barriers come from librtamd.so
 RCCL), so the bench runs on /opt/rocm's HIP runtime like the `ray` CLI; the
 RCCL id reaches the other ranks through rendezvous.py.
 
-After the timed region (never inside it): op-counted passes for the FLOP
-model, the wall-clock split of the CLI's end-to-end path (render + device
-toByte + D2H + parallel PNG, and the `ray` binary itself), kernel resources
-and occupancy, the trace kernel's HBM traffic from rocprofv3 PMC passes over
-the same frame, and the CPU baseline (the C port of the reference path,
-oracle/oracle.c, on a whole frame over the host cores plus a 1-thread band).
+A plain run sets up, warms up, times the K steps and prints the result line
+(headline value, ms_per_step, and the per-frame jitter / kernel / gather means
+the timed steps' own Stats give for free).  --dump-outputs DIR then writes
+what the last timed step left with its caller (dump_outputs below).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4]
+With --full, after the timed region (never inside it): op-counted passes for
+the FLOP model, the wall-clock split of the CLI's end-to-end path (render +
+device toByte + D2H + parallel PNG, and the `ray` binary itself), kernel
+resources and occupancy, the trace kernel's HBM traffic from rocprofv3 PMC
+passes over the same frame, the FP32 side leg, and the CPU baseline (the C
+port of the reference path, oracle/oracle.c, on a whole frame over the host
+cores plus a 1-thread band).  The --no-* switches and --fp32-steps trim --full.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -131,6 +137,36 @@ def ranks_block(kernel_ms: list, rng_ms: list, splits: list) -> dict:
     return out
 
 
+DUMP_MAX_PIXELS = 1_500_000    # 36 MB of RGB doubles + 12 MB of indices (the 4K frame is 199 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname: str, fb, rays: list) -> dict:
+    """--dump-outputs: what rt_render_dist left with its caller after the last
+    timed step, as float64 .npy files.  frame.npy: the framebuffer's RGB
+    doubles as [n, 3]; a frame of more than DUMP_MAX_PIXELS pixels is cut to
+    that many, drawn once without replacement by default_rng(DUMP_SEED) and
+    taken in ascending pixel order (frame_pixels.npy holds their row-major
+    indices), so two builds dump the same pixels.  rays.npy: the last step's
+    Stats counts [rays_intersect, rays_occluded, rays_traced] (the timers in
+    Stats differ from run to run and are left out)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    px = np.asarray(fb, dtype=np.float64).reshape(-1, 3)
+    n = px.shape[0]
+    if n > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_PIXELS, replace=False))
+    else:
+        idx = np.arange(n)
+    arrays = {"frame": np.ascontiguousarray(px[idx]), "frame_pixels": idx.astype(np.float64),
+              "rays": np.asarray(rays, dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "files": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "frame_pixels": int(len(idx)), "of": int(n)}
+
+
 def host_cpu() -> dict:
     """The CPU the baseline ran on (report nproc and the model)."""
     model = None
@@ -230,10 +266,16 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=4)
-    ap.add_argument("--cpu-rows", type=int, default=64, help="rows of the 1-thread CPU-oracle band")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 traffic passes")
-    ap.add_argument("--no-cli", action="store_true", help="skip the end-to-end CLI wall-clock leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frame (a fixed seeded pixel sample above "
+                         f"{DUMP_MAX_PIXELS} px) and ray counts as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the FLOP-model passes, the FP32 side leg, the CLI wall-clock "
+                         "leg, kernel occupancy, the rocprofv3 traffic passes and the CPU baseline")
+    ap.add_argument("--cpu-rows", type=int, default=64, help="rows of the 1-thread CPU-oracle band (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 traffic passes")
+    ap.add_argument("--no-cli", action="store_true", help="--full without the end-to-end CLI wall-clock leg")
     ap.add_argument("--no-cull", action="store_true", help="disable wave-uniform bound culling")
     ap.add_argument("--fp32", action="store_true",
                     help="time the NON-PARITY FP32 fast path as the headline (RT_FLAG_FP32); default is FP64")
@@ -360,6 +402,16 @@ def main() -> int:
     else:
         k_ms_max, rays_total, traced_total = k_ms, float(rays_local), float(traced_local)
 
+    # The last timed step's outputs as its caller holds them: the frame on
+    # rank 0, and the step's ray counts (summed over the ranks).
+    dumped = None
+    if args.dump_outputs:
+        last = [st.rays_intersect, st.rays_occluded, st.rays_traced]
+        if world > 1:
+            last = reduce_sum(last)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, frame.to_host(np.float64, (H, W, 3)), last)
+
     # Instrumented passes (outside the timed region) for the FLOP model:
     # culling off = the reference's own primitive calls one for one
     # (tests/test_gpu_parity.py::test_opcounts_match_reference_without_cull),
@@ -374,14 +426,16 @@ def main() -> int:
         d["_occluded"] = v[16]
         return d
 
-    ops_ref = counted_pass(flags | rtamd.RT_FLAG_COUNT_OPS | rtamd.RT_FLAG_NO_CULL)
-    ops_exe = counted_pass(flags | rtamd.RT_FLAG_COUNT_OPS)
-    rtamd.device_synchronize()
+    ops_ref = ops_exe = None
+    if args.full:
+        ops_ref = counted_pass(flags | rtamd.RT_FLAG_COUNT_OPS | rtamd.RT_FLAG_NO_CULL)
+        ops_exe = counted_pass(flags | rtamd.RT_FLAG_COUNT_OPS)
+        rtamd.device_synchronize()
 
     # Side leg (outside the timed region, not the headline): the NON-PARITY
     # FP32 fast path (RT_FLAG_FP32) on the same frame.
     fp32 = None
-    if args.fp32_steps > 0 and not args.fp32:
+    if args.full and args.fp32_steps > 0 and not args.fp32:
         st32 = rtamd.Stats()
         f32 = flags | rtamd.RT_FLAG_FP32
         step(f32, st32)
@@ -416,18 +470,51 @@ def main() -> int:
         teardown()
         return 0
 
+    value = rays_total / elapsed / 1e6
+    rays_per_frame = rays_total / args.steps
+    name = scenes.CONFIGS[args.config][0]
+    wall = {"rng": round(sum(rng_ms) / len(rng_ms), 3), "kernel": round(k_ms, 3),
+            "gather": round(sum(gather_ms) / len(gather_ms), 3)}
+    out = {
+        "metric": "Mrays/s (primary+secondary) + wall-clock per frame, 4K scene @1/2/4/8 GPU",
+        "value": round(value, 3),
+        "unit": "Mrays/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32" if args.fp32 else "f64",
+        "data": "synthetic: reference example scene JSON + mt19937(12345) jitter, rendered on device",
+        "config": {"workload": name, "width": W, "height": H, "mode": "paper" if mode else "standard",
+                   "rays_per_frame": int(rays_per_frame), "rays_traced_per_frame": int(traced_total / args.steps),
+                   "parallelism": f"{world} ranks, 1 GPU each: row-strips{30 if mode == 1 else 8}x{world}" +
+                                  (", RCCL ncclGather to rank 0 in 4 chunks" if world > 1 else ""),
+                   "cull": not args.no_cull},
+        "wall_clock_ms": wall,
+        "first_frame_ms": round(first_ms, 1),
+        "full": args.full,
+    }
+    if dumped is not None:
+        out["dumped"] = dumped
+    if ranks is not None:
+        out["ranks"] = ranks
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        barrier()
+        teardown()
+        return 0
+
     primary = H * W * (1 if mode == 1 else 8)
     flops, transc = model_flops(ops_ref, primary, mode == 1)
     flops_exe, _ = model_flops(ops_exe, primary, mode == 1)
     achieved = flops / (k_ms_max * 1e-3) / 1e12 / world   # per GPU: each rank's kernel covers 1/world of the frame
-    value = rays_total / elapsed / 1e6
-    rays_per_frame = rays_total / args.steps
 
     # Wall-clock split of the CLI's end-to-end path, N = 1:
     # render + device toByte + D2H of 3 B/px (rt_render_rgb8), the parallel
     # PNG deflate, and the `ray` binary itself (process start to exit).
-    wall = {"rng": round(sum(rng_ms) / len(rng_ms), 3), "kernel": round(k_ms, 3),
-            "gather": round(sum(gather_ms) / len(gather_ms), 3)}
     if world == 1:
         s8 = rtamd.Stats()
         rtamd.render_rgb8(sc, W, H, mode, 1, flags, s8)
@@ -505,7 +592,6 @@ def main() -> int:
         cpu["one_thread"] = {"value": round(cpu_rays / dt / 1e6, 4), "cores": 1,
                              "sample": f"output rows [{r0},{r1}) x {W} px, {cpu_rays} rays in {dt:.1f} s"}
 
-    name = scenes.CONFIGS[args.config][0]
     hbm = {"algorithmic_bytes_per_launch": alg_bytes,
            "algorithmic_GBs": round(alg_bytes / (k_ms * 1e-3) / 1e9, 1),
            "algorithmic_frac": round(alg_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
@@ -518,24 +604,7 @@ def main() -> int:
                                       "this run (FETCH x2, KiB -> B: MI355X_MICROARCH.md §HBM)"})
     elif traffic:
         hbm["counter_error"] = traffic.get("error")
-    out = {
-        "metric": "Mrays/s (primary+secondary) + wall-clock per frame, 4K scene @1/2/4/8 GPU",
-        "value": round(value, 3),
-        "unit": "Mrays/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32" if args.fp32 else "f64",
-        "data": "synthetic: reference example scene JSON + mt19937(12345) jitter, rendered on device",
-        "config": {"workload": name, "width": W, "height": H, "mode": "paper" if mode else "standard",
-                   "rays_per_frame": int(rays_per_frame), "rays_traced_per_frame": int(traced_total / args.steps),
-                   "parallelism": f"{world} ranks, 1 GPU each: row-strips{30 if mode == 1 else 8}x{world}" +
-                                  (", RCCL ncclGather to rank 0 in 4 chunks" if world > 1 else ""),
-                   "cull": not args.no_cull},
+    out.update({
         "roofline": {"bound": "fp64-valu", "achieved": round(achieved, 3), "peak": FP64_VALU_PEAK_TFLOPS,
                      "unit": "TFLOP/s", "frac": round(achieved / FP64_VALU_PEAK_TFLOPS, 4),
                      "traffic": traffic_bytes, "kernel": kernel_name,
@@ -545,13 +614,9 @@ def main() -> int:
                      "executed_flops_per_launch": flops_exe / world,
                      "executed_frac": round(flops_exe / world / (k_ms_max * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS, 4),
                      "occupancy": occupancy, "hbm": hbm},
-        "wall_clock_ms": wall,
-        "first_frame_ms": round(first_ms, 1),
         "cpu_baseline": cpu,
         "fp32_fast_path": fp32,
-    }
-    if ranks is not None:
-        out["ranks"] = ranks
+    })
     print(json.dumps(out), flush=True)
     barrier()
     teardown()

@@ -88,6 +88,65 @@ def test_ranks_block_schema_synthetic():
     assert blk["kernel_ms"]["max"] == 1.2 and blk["placement_ms"]["root_total"] == 0.3
 
 
+def test_dump_outputs_whole_frame_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs' writer (no GPU): a small frame is written whole; a
+    frame above DUMP_MAX_PIXELS is cut to that many pixels, the same ones on
+    every call, in ascending order, as float64."""
+    import numpy as np
+
+    b = _bench_module()
+    fb = np.random.default_rng(7).random((9, 11, 3))
+    info = b.dump_outputs(str(tmp_path / "whole"), fb, [5, 6, 7])
+    assert (info["frame_pixels"], info["of"]) == (99, 99)
+    assert np.array_equal(np.load(tmp_path / "whole" / "frame.npy"), fb.reshape(-1, 3))
+    assert np.array_equal(np.load(tmp_path / "whole" / "rays.npy"), [5.0, 6.0, 7.0])
+
+    monkeypatch.setattr(b, "DUMP_MAX_PIXELS", 40)
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), fb, [5, 6, 7])
+    idx = np.load(tmp_path / "s1" / "frame_pixels.npy")
+    got = np.load(tmp_path / "s1" / "frame.npy")
+    assert idx.dtype == np.float64 and got.dtype == np.float64 and got.shape == (40, 3)
+    assert (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < 99
+    assert np.array_equal(got, fb.reshape(-1, 3)[idx.astype(np.int64)])
+    for name in ("frame", "frame_pixels", "rays"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_timed_frame(gpu, tmp_path):
+    """A plain `bench.py --steps K --dump-outputs DIR` on config 2: the line
+    carries the headline fields and none of the --full legs, K sets the timed
+    steps, and the dumped frame and ray counts are what a render of the same
+    scene returns in this (another) process, bit for bit."""
+    import numpy as np
+
+    import scenes
+
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--config", "2", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "a")], capture_output=True, text=True, timeout=120,
+                       env=_clean_env(), cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    (line,) = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert (line["steps"], line["warmup"], line["n_gpus"], line["dtype"], line["unit"]) == (3, 1, 1, "f64", "Mrays/s")
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["full"] is False
+    assert not {"roofline", "cpu_baseline", "fp32_fast_path"} & set(line)
+    assert set(line["wall_clock_ms"]) == {"rng", "kernel", "gather"}
+
+    text, mode = scenes.config_json(2)
+    sc = gpu.load_scene_from_json_text(text)
+    st = gpu.Stats()
+    fb = gpu.Tracer(sc, sc.width, sc.height, mode).render(st)
+    frame = np.load(tmp_path / "a" / "frame.npy")
+    idx = np.load(tmp_path / "a" / "frame_pixels.npy").astype(np.int64)
+    assert frame.dtype == np.float64 and line["dumped"]["of"] == sc.width * sc.height
+    assert np.array_equal(frame, fb.reshape(-1, 3)[idx])
+    rays = np.load(tmp_path / "a" / "rays.npy")
+    assert list(rays[:2]) == [st.rays_intersect, st.rays_occluded]
+    assert line["config"]["rays_per_frame"] == st.rays_intersect + st.rays_occluded
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 8])
 def test_ranks_block_from_thread_ranks(gpu, world):

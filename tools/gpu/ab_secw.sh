@@ -11,5 +11,5 @@ for v in head cur "$@"; do
   esac
   echo "== $v"
   RTAMD_LIB=$L timeout -k 10 300 python tools/secw_base.py 2>&1 | grep -v amdgpu.ids || exit 1
-  RTAMD_LIB=$L timeout -k 10 200 python bench.py --config 6 --no-cpu --no-pmc --no-cli --fp32-steps 0 --steps 50 --warmup 3 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cfg 6 frame_ms', d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'])" || exit 1
+  RTAMD_LIB=$L timeout -k 10 200 python bench.py --full --config 6 --no-cpu --no-pmc --no-cli --fp32-steps 0 --steps 50 --warmup 3 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cfg 6 frame_ms', d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'])" || exit 1
 done
