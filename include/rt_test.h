@@ -49,8 +49,10 @@ int rt_test_wave_bvh(const struct rt_scene* s, int32_t* counts, int32_t* worig, 
  * culling variant, reflection/refraction variant}.  Needs a device. */
 int rt_test_kernel_info(const struct rt_scene* s, int mode, int flags, int32_t* out);
 
-/* The name of that kernel as rocprofv3 reports it (e.g. "rtd::k_std_lean<false, true>"),
- * NUL-terminated into out[0 .. cap).  Host only. */
+/* The name of that kernel as rocprofv3 reports it (e.g. "rtd::k_std_lean<false, 1, false>"),
+ * NUL-terminated into out[0 .. cap): the frame's own kernel choice
+ * (frame_plan.hpp pick_variant) looked up in the launch tables, so a scene a
+ * frame refuses (RT_ERR_UNSUPPORTED) is refused here too.  Host only. */
 int rt_test_kernel_name(const struct rt_scene* s, int mode, int flags, char* out, int cap);
 
 /* GPU: the shared-denominator division of the device code (rt_device.hpp
@@ -142,7 +144,41 @@ int rt_test_pokeball_thresholds(double btn_outer, double ring_width, double* out
  * (rtamd::paper_code_value): bits 0-2 edge index in {0, 0.3, 0.5, 0.6, 0.9},
  * bit 3 halved at the frame border, bit 4 the hatch bit (white). */
 double rt_test_paper_code_value(int code);
-/* CPU: the paper-mode primary launch order (rt_render.hip order_paper_groups)
+/* CPU: the frame planners of csrc/host/frame_plan.hpp, the host-only code
+ * rt_render.hip and rt_dist.hip execute.  All return an rt_status.
+ *
+ * rt_test_plan_dist: rank's part of an H-row frame over `world` ranks
+ * (plan_dist_frame; kind 0 = FP64 output, the root sheds strips by mode,
+ * 1 = RGB8, no shed; chunks 1..4): counts[3] = {n rows, m = rows of the
+ * fullest rank, n chunks}, rows_out[n], bounds_out[2 * n chunks] = (a, b) of
+ * every chunk of [0, m), and with rowtab_out (cap_table >= world * m ints)
+ * the root's placement table: slot world*a + r*(b-a) + (i-a) holds rank r's
+ * i-th row, -1 padding. */
+int rt_test_plan_dist(int H, int world, int rank, int mode, int kind, int chunks, int32_t* counts, int32_t* rows_out,
+                      int32_t* bounds_out, int32_t* rowtab_out, int cap_table);
+/* rt_test_plan_std: the standard-mode jitter layout of `rows` (distinct, in
+ * [0, H)): jrow_out[n_rows], ranges_out[3 * n ranges] = (qa, qb, dst) of the
+ * coalesced stream ranges (room for 3 * n_rows), out3 = {n ranges, q_end,
+ * checkpoints needed}. */
+int rt_test_plan_std(int W, int H, const int32_t* rows, int n_rows, int32_t* jrow_out, int64_t* ranges_out,
+                     int64_t* out3);
+/* rt_test_plan_paper: the paper-mode frame plan of `rows`: ext_out[n_ext] the
+ * rows needing a primary hit and ext_shade_out[n_ext] (room for H each),
+ * ext_pos_out[H], nbr_out[3 * n_rows], out6 = {n_ext, logical intersect
+ * calls, ints of the aux buffer, list capacity, gtime words, waves per list
+ * group}. */
+int rt_test_plan_paper(int W, int H, const int32_t* rows, int n_rows, int32_t* ext_out, int32_t* ext_shade_out,
+                       int32_t* ext_pos_out, int32_t* nbr_out, int64_t* out6);
+/* rt_test_plan_paper_calls: that frame's trace calls calls[3k ..] = (ri0,
+ * ri1, stream id), k < n_calls <= 30, through PaperCalls::next_call; after
+ * call rollback_after (-1: never) rollback() is called.  call_out[4k ..] =
+ * {ok, list offset, list length, bit mask of the calls it waits for}; the
+ * lists back to back in lists_out (cap_lists ints); ext_done_out[n_ext] = the
+ * final marks (call index + 1, 0 = not computed). */
+int rt_test_plan_paper_calls(int W, int H, const int32_t* rows, int n_rows, const int32_t* calls, int n_calls,
+                             int rollback_after, int32_t* call_out, int32_t* lists_out, int cap_lists,
+                             int32_t* ext_done_out);
+/* CPU: the paper-mode primary launch order (frame_plan.hpp order_paper_groups)
  * applied in place to list[0, n) (n a multiple of 16; entries are ext
  * indices, -1 padding), given the measured cost of the 8-entry group whose
  * first entry is e in cost[e] (0 = unmeasured).  Returns 0. */

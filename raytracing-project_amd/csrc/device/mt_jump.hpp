@@ -6,6 +6,8 @@
 
 #include <vector>
 
+#include "frame_plan.hpp"   // JRange
+
 namespace rtamd {
 
 // Checkpoint c (segment c of K twist blocks) is stored as up to kMTParts
@@ -31,15 +33,6 @@ struct JitterPlan {
     void* h_stage = nullptr;
     void drop_stage();
     void release();
-};
-
-// A run of stream outputs: the draw made of outputs q, q+1 (q even, in
-// [qa, qb)) is stored at jit[dst + (q - qa)/2].  Ranges passed to the
-// launcher are sorted by qa and disjoint.  A rendered loop row y of width W
-// is the range [32*W*y, 32*W*(y+1)) (tracer.cpp:284-293: 8 samples x 2
-// draws x 2 words).
-struct JRange {
-    int64_t qa, qb, dst;
 };
 
 // mt19937 tempering (libstdc++ random.tcc operator()).

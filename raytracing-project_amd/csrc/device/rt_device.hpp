@@ -296,7 +296,7 @@ struct Cnt<true> {
 };
 // The plain kernels' counter type (no counting, like Cnt<false>): scenes
 // whose objects are all spheres, half-spaces and pokeballs (no transform or
-// CSG object, SceneView::plain) run kernels compiled without the transform /
+// CSG object, KernelVariant::plain) run kernels compiled without the transform /
 // CSG evaluation and the CSG shadow prefilters.  That code, never executed
 // for such scenes, still shaped the register allocation of every path: the
 // paper kernel spilled 48 B/lane and the recursion kernel 48 B beyond its

@@ -2,8 +2,10 @@
 //
 // pixels are independent, so a frame is partitioned by OUTPUT
 // ROWS: strips of RT_STRIP_ROWS rows (paper mode: RT_PAPER_STRIP_ROWS) are
-// dealt to the ranks interleaved (strip_owners: balances cheap sky rows
-// against expensive geometry rows).  Every rank runs
+// dealt to the ranks interleaved (balances cheap sky rows against expensive
+// geometry rows).  The partition, its chunks and the root's placement table
+// are host-only code (csrc/host/frame_plan.hpp plan_dist_frame); this file
+// executes that plan.  Every rank runs
 // the ordinary trace (rt_frame_* of rt_render.hip) on its rows, chunk by
 // chunk, and each chunk is handed to ONE RCCL collective, ncclGather to rank
 // 0 over xGMI, on a high-priority stream so it overlaps the tracing of the
@@ -41,28 +43,15 @@
 #include <vector>
 
 #include "rt.h"
+#include "rt_devbuf.hpp"
 #include "rt_internal.hpp"
 #include "rt_launch.hpp"
 #include "rt_test.h"
 
 namespace {
 
-constexpr int kChunks = 4;
-// Paper frames gather one code byte per pixel, so their chunks hide little
-// transfer, while every chunk adds a launch tail of the costly paper waves:
-// 2 chunks project config 5 at 8 ranks 5.21-5.23x -> 5.46-5.56x, at 4 ranks
-// 3.04 -> 3.12-3.18x (1: 4.58x, 3: 5.30x; profiles/r06_ab/ab_dist_chunks.txt).
-constexpr int kPaperChunks = 2;
-constexpr int kSplitSlots = 10;   // rt_dist_frame_split (include/rt.h)   // pipeline units per rank (chunk k gathered while k+1 is traced)
-
-#define HIP_TRY(expr)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) {                                                                  \
-            rtamd::set_last_error(std::string(#expr) + " failed: " + hipGetErrorString(e_));     \
-            return RT_ERR_HIP;                                                                   \
-        }                                                                                        \
-    } while (0)
+using rtamd::kChunks;   // (bounds the per-chunk event arrays)
+constexpr int kSplitSlots = 10;   // rt_dist_frame_split (include/rt.h)
 
 #define NCCL_TRY(expr)                                                                           \
     do {                                                                                         \
@@ -73,102 +62,7 @@ constexpr int kSplitSlots = 10;   // rt_dist_frame_split (include/rt.h)   // pip
         }                                                                                        \
     } while (0)
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        const size_t want = bytes + bytes / 16 + 256;
-        rtamd::SetupTimer tm(rtamd::kSetupAlloc);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// ------------------------------------------------------------- partition
-// Strip height per mode: standard mode RT_STRIP_ROWS (8); paper mode
-// RT_PAPER_STRIP_ROWS (30): each strip's primary hits are traced with its two
-// neighbour rows (the edge probes, tracer.cpp:133-178), and 30 + 2 = 32 rows
-// keep every 8-row wave of k_paper_primary inside one strip (coherent rays
-// for the wave-level culls) at 1/15 halo overhead (8-row strips: 1/4 extra
-// rows and waves straddling strips 16+ rows apart).
-int strip_height(int mode) { return mode == RT_MODE_PAPER ? RT_PAPER_STRIP_ROWS : RT_STRIP_ROWS; }
-
-// Which rank renders strip s.  Interleaved so that every rank samples the
-// whole frame (cheap sky rows against expensive geometry rows), by a smooth
-// weighted round robin: every strip, each rank's credit grows by its weight
-// and the rank with the most credit takes the strip (and pays the total).
-//  * Ties go to the rank first in a per-round rotation (round k = strips
-//    [k*world, (k+1)*world) starts at rank k mod world), so a rank's strips do
-//    not all sit at the same phase of a world*S-row period: config 5's sphere
-//    rows have structure on that scale (a plain s mod world split left the
-//    slowest of 8 paper-mode ranks 11 % above the mean).
-//  * Rank 0 also places every gathered strip into the frame (the FP64 frame:
-//    24 B/px written; paper mode decodes one byte per pixel into 24), so it
-//    renders fewer strips: weight 1 - c*world (per mille: c = 45 paper, 8
-//    standard, 0 for RGB8 output; from per-rank timings, profiles/r04*; the
-//    paper value raised 30 -> 45 with the plain paper kernel, whose faster
-//    trace left the root's placement the longest leg: 8-rank frame
-//    0.726 -> 0.708 ms, profiles/r06_ab/ab_dist_shed_plain.txt).
-// The partition is a pure function of (H, world, mode, kind), all of which
-// the ranks check against each other before the first gather.
-constexpr int kRootShedPaper = 45, kRootShedStd = 8;
-// (RT_ROOT_SHED_PAPER / RT_ROOT_SHED_STD: measurement A/B only.  Both values
-// travel in the frame descriptor, so ranks that see different ones refuse the
-// frame together instead of tracing another partition than the root places.)
-int64_t root_shed(int mode) {
-    static const int shed_paper = [] { const char* e = std::getenv("RT_ROOT_SHED_PAPER"); return e && *e ? std::atoi(e) : kRootShedPaper; }();
-    static const int shed_std = [] { const char* e = std::getenv("RT_ROOT_SHED_STD"); return e && *e ? std::atoi(e) : kRootShedStd; }();
-    return mode == RT_MODE_PAPER ? shed_paper : shed_std;
-}
-std::vector<int> strip_owners(int n_strips, int world, int64_t c) {
-    std::vector<int> own((size_t)std::max(0, n_strips), 0);
-    if (world <= 1) return own;
-    std::vector<int64_t> w((size_t)world, 1000), cur((size_t)world, 0);
-    w[0] = std::max<int64_t>(500, 1000 - c * world);
-    int64_t total = 0;
-    for (int64_t v : w) total += v;
-    for (int s = 0; s < n_strips; ++s) {
-        for (int r = 0; r < world; ++r) cur[r] += w[r];
-        const int rot = (s / world) % world;
-        int best = rot;
-        for (int i = 1; i < world; ++i) {
-            const int r = (rot + i) % world;
-            if (cur[r] > cur[best]) best = r;
-        }
-        own[s] = best;
-        cur[best] -= total;
-    }
-    return own;
-}
-
-// Output rows of every rank (ascending per rank), strips of strip_height(mode).
-// (A partition balanced on measured strip costs - the strips' summed primary
-// wave ticks, exchanged in the trace-status agreement, longest processing
-// time first - was measured and rejected: slower at 2 ranks, no better at 4
-// and 8, profiles/r05_ab/ab_cost_partition.txt.)
-// shed: the root's per-mille shed for this frame (0 for RGB8 output; else
-// root_shed(mode), which every rank checks in the frame descriptor).
-std::vector<std::vector<int32_t>> partition_rows(int H, int world, int mode, int64_t shed) {
-    const int S = strip_height(mode);
-    const int n_strips = (H + S - 1) / S;
-    std::vector<std::vector<int32_t>> rows((size_t)world);
-    const std::vector<int> own = strip_owners(n_strips, world, shed);
-    for (int st = 0; st < n_strips; ++st)
-        for (int r = st * S; r < std::min(H, (st + 1) * S); ++r) rows[own[st]].push_back(r);
-    return rows;
-}
+using DevBuf = rtamd::DevBufT<16>;   // (growth slack 1/16)
 
 uint64_t fnv_bytes(uint64_t h, const void* p, size_t n) {
     const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -202,13 +96,6 @@ int64_t scene_hash(const rt_scene* s) {
     h = fnv_bytes(h, d.dir_lights, sizeof(rt_dir_light) * (size_t)d.n_dir_lights);
     return (int64_t)(h >> 2);   // (62 bits: v and -v both representable)
 }
-
-// Row chunks of a rank's share: rtamd::row_chunks (rt_render.hip), whole
-// strips of S rows (a chunk never splits a strip, so a paper-mode strip's
-// rows and halo are traced by one launch), of decreasing size (4 chunks:
-// 40/30/20/10 %).  Chunk k is gathered while chunk k+1 is traced, so only the
-// last, smallest chunk's gather is exposed.
-std::vector<std::pair<int, int>> chunk_bounds(int m, int chunks, int S = 1) { return rtamd::row_chunks(m, chunks, S); }
 
 // Gathered slot i (row_bytes bytes) -> row rows[i] of dst; rows[i] < 0 is padding.
 template <class V>
@@ -464,7 +351,7 @@ int dist_init_streams(rt_dist& D, bool coll, bool alt) {
 // RT_ERR_HIP instead of hanging.
 // Descriptor: W, H, mode, output kind, flags, the scene's content hash
 // (ranks that loaded different scenes refuse the frame together) and the
-// root's strip shed of each mode (strip_owners: a rank that saw another
+// root's strip shed of each mode (frame_plan.hpp strip_owners: a rank that saw another
 // RT_ROOT_SHED_* value would trace another partition than the root places).
 constexpr int kDescFields = 8;
 
@@ -636,16 +523,6 @@ __global__ void k_test_stall(unsigned long long max_ticks) {
 
 enum { kInjectTraceFail = 1, kInjectStall = 2, kInjectSetupFail = 3 };
 
-// Row chunks per rank and frame (each one gather): kChunks (paper: kPaperChunks), or
-// RT_DIST_CHUNKS (standard mode) / RT_DIST_CHUNKS_PAPER from the environment
-// (measurement A/B; 1 .. kChunks).
-int frame_chunks(int mode) {
-    static const int c[2] = {
-        [] { const char* e = std::getenv("RT_DIST_CHUNKS"); return e && *e ? std::atoi(e) : kChunks; }(),
-        [] { const char* e = std::getenv("RT_DIST_CHUNKS_PAPER"); return e && *e ? std::atoi(e) : kPaperChunks; }()};
-    return std::min(kChunks, std::max(1, c[mode == RT_MODE_PAPER ? 1 : 0]));
-}
-
 // RT_DIST_TIMEOUT_MS: how long a rank waits for its peers inside one frame
 // before it aborts the communicator (default 120 s).
 double env_timeout_ms() {
@@ -674,7 +551,8 @@ int dist_frame(rt_dist& D, const rt_scene* s, int W, int H, int mode, int flags,
     const bool coll = D.collective();
     const int inject = D.inject;
     D.inject = 0;
-    const int64_t shed_std = root_shed(RT_MODE_STANDARD) + D.shed_delta, shed_paper = root_shed(RT_MODE_PAPER) + D.shed_delta;
+    const int64_t shed_std = rtamd::root_shed(RT_MODE_STANDARD) + D.shed_delta,
+                  shed_paper = rtamd::root_shed(RT_MODE_PAPER) + D.shed_delta;
     D.shed_delta = 0;
     // Local argument checks.  Without a collective they return at once; in a
     // collective frame a failing rank still joins the frame's agreement (below)
@@ -691,7 +569,6 @@ int dist_frame(rt_dist& D, const rt_scene* s, int W, int H, int mode, int flags,
         if (rs != RT_OK) return rs;
     }
     const int Wc = std::max(W, 1), Hc = std::max(H, 1);
-    const int S = strip_height(mode == RT_MODE_PAPER ? RT_MODE_PAPER : RT_MODE_STANDARD);
     int64_t shash = 0;   // (the scene's content hash, checked with the descriptor)
     if (s) {
         const uint64_t uid = rtamd::scene_uid(s);
@@ -708,22 +585,21 @@ int dist_frame(rt_dist& D, const rt_scene* s, int W, int H, int mode, int flags,
         const int rx = dist_init_xchg(D, n_desc + n_stat);
         if (rx != RT_OK) return rx;
     }
-    const std::vector<std::vector<int32_t>> part =
-        partition_rows(Hc, D.world, mode, kind ? 0 : (mode == RT_MODE_PAPER ? shed_paper : shed_std));
-    const std::vector<int32_t>& rows = part[D.rank];
-    const int n = (int)rows.size();
-    int m = 0;
-    for (const auto& pr : part) m = std::max(m, (int)pr.size());
+    // this rank's rows, their chunks (one GPU: paper frames in chunks too, so
+    // that each chunk's finish pass overlaps the next chunk's primary on the
+    // other stream) and, on a collective frame's root, the placement table
+    rtamd::DistPlan plan = rtamd::plan_dist_frame(
+        Hc, D.world, D.rank, mode, kind ? 0 : (mode == RT_MODE_PAPER ? shed_paper : shed_std),
+        std::min(kChunks, coll ? rtamd::frame_chunks(mode) : (mode == RT_MODE_PAPER ? rtamd::paper_chunks_1gpu() : 1)),
+        coll && root);
+    const std::vector<int32_t>& rows = plan.rows;
+    const std::vector<std::pair<int, int>>& bounds = plan.bounds;
+    const int n = (int)rows.size(), m = plan.m;
     const size_t row_elems = (size_t)Wc * 3;
     // paper mode (FP64) across ranks: each rank produces one paper-code byte
     // per pixel, 1 B/px crosses xGMI, and the root decodes (k_place_codes)
     const bool codes = coll && mode == RT_MODE_PAPER && !(flags & RT_FLAG_FP32);
     const size_t row_bytes = codes ? (size_t)Wc : row_elems * (kind ? 1 : sizeof(double));   // gathered per row
-    // (one GPU: paper frames in chunks too, so that each chunk's finish pass
-    // overlaps the next chunk's primary on the other stream)
-    // (kChunks bounds the per-chunk event arrays)
-    const auto bounds = chunk_bounds(
-        m, std::min(kChunks, coll ? frame_chunks(mode) : (mode == RT_MODE_PAPER ? rtamd::paper_chunks_1gpu() : 1)), S);
     const bool direct = !coll && kind == 0;   // trace straight into the caller's frame
     DevBuf& stage = D.sim_stage ? *D.sim_stage : D.stage;
     auto fail = [&](int code, const char* what) {
@@ -741,15 +617,7 @@ int dist_frame(rt_dist& D, const rt_scene* s, int W, int H, int mode, int flags,
     if (rc == RT_OK && coll && (root || D.sim_stage) && stage.ensure((size_t)D.world * m * row_bytes) != hipSuccess)
         fail(RT_ERR_HIP, "gather stage allocation failed");
     if (rc == RT_OK && coll && root) {
-        // placement table: chunk k occupies slots [world*a, world*b) as [rank][b-a]
-        D.rowtab_host.assign((size_t)D.world * m, -1);
-        for (int r = 0; r < D.world; ++r) {
-            const std::vector<int32_t>& rr = part[r];
-            for (const auto& ab : bounds)
-                for (int i = ab.first; i < ab.second; ++i)
-                    D.rowtab_host[(size_t)D.world * ab.first + (size_t)r * (ab.second - ab.first) + (i - ab.first)] =
-                        i < (int)rr.size() ? rr[i] : -1;
-        }
+        D.rowtab_host.swap(plan.rowtab);   // (the source of the async upload: kept with the rank)
         if (D.rowtab.ensure(D.rowtab_host.size() * sizeof(int32_t)) != hipSuccess ||
             hipMemcpyAsync(D.rowtab.p, D.rowtab_host.data(), D.rowtab_host.size() * sizeof(int32_t),
                            hipMemcpyHostToDevice, D.comm_st) != hipSuccess)
@@ -1220,7 +1088,7 @@ extern "C" int rt_dist_rows_mode(int H, int world, int rank, int mode, int32_t* 
     if (H <= 0 || world <= 0 || rank < 0 || rank >= world || !rows_out ||
         (mode != RT_MODE_STANDARD && mode != RT_MODE_PAPER))
         return RT_ERR_INVALID_ARG;
-    const std::vector<int32_t> r = partition_rows(H, world, mode, root_shed(mode))[rank];
+    const std::vector<int32_t> r = rtamd::partition_rows(H, world, mode, rtamd::root_shed(mode))[rank];
     std::copy(r.begin(), r.end(), rows_out);
     return (int)r.size();
 }

@@ -295,7 +295,7 @@ __device__ __forceinline__ void paper_primary_body(const DevScene& S, const Pape
     const int ei = li < P.n_list ? P.ext_list[li] : -1;
     const bool active = x < P.W && ei >= 0;
     // T (timed launches, P.gtime set): the wave's cost for later frames'
-    // launch order (rt_render.hip order_paper_groups), its start and end
+    // launch order (frame_plan.hpp order_paper_groups), its start and end
     // wall-clock ticks, stored into its own slot at the end (one-address
     // atomics per list group serialised the waves: +18 % frame time).  Every
     // store of this kernel comes after its last scene read, and only timed
@@ -599,143 +599,141 @@ constexpr size_t kStdPool = pool_bytes(kStdThreads), kPaperPool = pool_bytes(kPa
 // the paper primary's grid from the host's 16x16-pixel units
 inline dim3 pgrid(dim3 g) { return kPaperWPB == 4 ? g : dim3(2 * g.x, 2 * g.y); }
 
-// The plain kernels (PL) are built for the FP64 namespace only (RT_NO_PLAIN:
-// the FP32 diagnostic build keeps one variant per choice).
-#ifdef RT_NO_PLAIN
-constexpr bool kPlainKernels = false;
-#else
-constexpr bool kPlainKernels = true;
+// The trace kernels by variant: one table per mode, each kernel written once
+// with its template arguments spelled out, so that an entry's name is the
+// instantiation as rocprofv3 prints it.  (The untimed k_paper_primary entries
+// leave T at its default: the name rt_test_kernel_name has always reported.)
+// Columns: E D SEC C WV PL (T), the KernelVariant fields an entry answers to
+// (frame_plan.hpp pick_variant produces only canonical variants).
+// RT_GENERAL_ONLY (the big-stack build) keeps the general E = D = true rows,
+// RT_NO_PLAIN (the FP32 diagnostic build) drops the PL rows: a variant
+// without a row has no kernel in this namespace, and its launch is an error.
+constexpr unsigned vkey(bool e, bool d, bool sec, bool c, int wv, bool pl, bool t) {
+    return (unsigned)e | (unsigned)d << 1 | (unsigned)sec << 2 | (unsigned)c << 3 | (unsigned)pl << 4 |
+           (unsigned)t << 5 | (unsigned)wv << 6;
+}
+template <class P>
+struct KernelRow {
+    unsigned key;
+    void (*fn)(DevScene, P);
+    const char* name;
+};
+#define RT_ROW(e, d, sec, c, wv, pl, t, ...) {vkey(e, d, sec, c, wv, pl, t), __VA_ARGS__, #__VA_ARGS__}
+#define RT_STD(e, d, sec, c, wv, pl, ...) RT_ROW(e, d, sec, c, wv, pl, 0, __VA_ARGS__)
+#define RT_PAP(e, d, c, wv, pl, t, ...) RT_ROW(e, d, 0, c, wv, pl, t, __VA_ARGS__)
+const KernelRow<StdParams> kStdKernels[] = {
+    RT_STD(1, 1, 0, 0, 0, 0, k_std<true, true, false, false, false>),
+    RT_STD(1, 1, 0, 1, 0, 0, k_std<true, true, false, true, false>),
+    RT_STD(1, 1, 1, 0, 0, 0, k_std<true, true, true, false, false>),
+    RT_STD(1, 1, 1, 1, 0, 0, k_std<true, true, true, true, false>),
+#ifndef RT_GENERAL_ONLY
+    RT_STD(0, 1, 0, 0, 0, 0, k_std<false, true, false, false, false>),
+    RT_STD(0, 1, 0, 1, 0, 0, k_std<false, true, false, true, false>),
+    RT_STD(0, 1, 1, 0, 0, 0, k_std<false, true, true, false, false>),
+    RT_STD(0, 1, 1, 1, 0, 0, k_std<false, true, true, true, false>),
+    RT_STD(0, 0, 1, 0, 0, 0, k_std<false, false, true, false, false>),   // (reflection without wave culls)
+    RT_STD(0, 0, 1, 1, 0, 0, k_std<false, false, true, true, false>),
+    RT_STD(0, 0, 0, 0, 0, 0, k_std_lean<false, 0, false>),
+    RT_STD(0, 0, 0, 0, 1, 0, k_std_lean<false, 1, false>),
+    RT_STD(0, 0, 0, 0, 2, 0, k_std_lean<false, 2, false>),
+    RT_STD(0, 0, 0, 1, 0, 0, k_std_lean<true, 0, false>),
+    RT_STD(0, 0, 0, 1, 1, 0, k_std_lean<true, 1, false>),
+    RT_STD(0, 0, 0, 1, 2, 0, k_std_lean<true, 2, false>),
+    RT_STD(0, 0, 1, 0, 1, 0, k_std_secw<false, 1, false>),
+    RT_STD(0, 0, 1, 0, 2, 0, k_std_secw<false, 2, false>),
+    RT_STD(0, 0, 1, 1, 1, 0, k_std_secw<true, 1, false>),
+    RT_STD(0, 0, 1, 1, 2, 0, k_std_secw<true, 2, false>),
+#ifndef RT_NO_PLAIN
+    RT_STD(0, 0, 0, 0, 0, 1, k_std_lean<false, 0, true>),
+    RT_STD(0, 0, 0, 0, 1, 1, k_std_lean<false, 1, true>),
+    RT_STD(0, 0, 0, 0, 2, 1, k_std_lean<false, 2, true>),
+    RT_STD(0, 0, 1, 0, 1, 1, k_std_secw<false, 1, true>),
+    RT_STD(0, 0, 1, 0, 2, 1, k_std_secw<false, 2, true>),
 #endif
-template <int WV>
-void launch_lean(bool c, bool pl, dim3 grid, hipStream_t st, const DevScene& S, const StdParams& P) {
-    if (c) hipLaunchKernelGGL((k_std_lean<true, WV>), grid, dim3(kStdThreads), kStdPool, st, S, P);
-    else if (kPlainKernels && pl) hipLaunchKernelGGL((k_std_lean<false, WV, kPlainKernels>), grid, dim3(kStdThreads), kStdPool, st, S, P);
-    else hipLaunchKernelGGL((k_std_lean<false, WV>), grid, dim3(kStdThreads), kStdPool, st, S, P);
-}
-template <int WV>
-void launch_secw(bool c, bool pl, dim3 grid, hipStream_t st, const DevScene& S, const StdParams& P) {
-    if (c) hipLaunchKernelGGL((k_std_secw<true, WV>), grid, dim3(kStdThreads), kStdPool, st, S, P);
-    else if (kPlainKernels && pl) hipLaunchKernelGGL((k_std_secw<false, WV, kPlainKernels>), grid, dim3(kStdThreads), kStdPool, st, S, P);
-    else hipLaunchKernelGGL((k_std_secw<false, WV>), grid, dim3(kStdThreads), kStdPool, st, S, P);
-}
-template <int WV>
-void launch_paper_lean(bool c, bool pl, dim3 grid, hipStream_t st, const DevScene& S, const PaperParams& P) {
-    // (timed launches: never op-counting ones, rt_frame_trace)
-    if (c) hipLaunchKernelGGL((k_paper_primary_lean<true, WV>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
-    else if (kPlainKernels && pl) {
-        if (P.gtime) hipLaunchKernelGGL((k_paper_primary_lean<false, WV, true, kPlainKernels>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
-        else hipLaunchKernelGGL((k_paper_primary_lean<false, WV, false, kPlainKernels>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
-    } else if (P.gtime) hipLaunchKernelGGL((k_paper_primary_lean<false, WV, true>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
-    else hipLaunchKernelGGL((k_paper_primary_lean<false, WV>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
-}
+#endif
+};
+// (timed launches: never op-counting ones, rt_frame_trace)
+const KernelRow<PaperParams> kPaperKernels[] = {
+    RT_PAP(1, 1, 0, 0, 0, 0, k_paper_primary<true, true, false>),
+    RT_PAP(1, 1, 0, 0, 0, 1, k_paper_primary<true, true, false, true>),
+    RT_PAP(1, 1, 1, 0, 0, 0, k_paper_primary<true, true, true>),
+#ifndef RT_GENERAL_ONLY
+    RT_PAP(0, 1, 0, 0, 0, 0, k_paper_primary<false, true, false>),
+    RT_PAP(0, 1, 0, 0, 0, 1, k_paper_primary<false, true, false, true>),
+    RT_PAP(0, 1, 1, 0, 0, 0, k_paper_primary<false, true, true>),
+    RT_PAP(0, 0, 0, 0, 0, 0, k_paper_primary_lean<false, 0, false, false>),
+    RT_PAP(0, 0, 0, 1, 0, 0, k_paper_primary_lean<false, 1, false, false>),
+    RT_PAP(0, 0, 0, 2, 0, 0, k_paper_primary_lean<false, 2, false, false>),
+    RT_PAP(0, 0, 0, 0, 0, 1, k_paper_primary_lean<false, 0, true, false>),
+    RT_PAP(0, 0, 0, 1, 0, 1, k_paper_primary_lean<false, 1, true, false>),
+    RT_PAP(0, 0, 0, 2, 0, 1, k_paper_primary_lean<false, 2, true, false>),
+    RT_PAP(0, 0, 1, 0, 0, 0, k_paper_primary_lean<true, 0, false, false>),
+    RT_PAP(0, 0, 1, 1, 0, 0, k_paper_primary_lean<true, 1, false, false>),
+    RT_PAP(0, 0, 1, 2, 0, 0, k_paper_primary_lean<true, 2, false, false>),
+#ifndef RT_NO_PLAIN
+    RT_PAP(0, 0, 0, 0, 1, 0, k_paper_primary_lean<false, 0, false, true>),
+    RT_PAP(0, 0, 0, 1, 1, 0, k_paper_primary_lean<false, 1, false, true>),
+    RT_PAP(0, 0, 0, 2, 1, 0, k_paper_primary_lean<false, 2, false, true>),
+    RT_PAP(0, 0, 0, 0, 1, 1, k_paper_primary_lean<false, 0, true, true>),
+    RT_PAP(0, 0, 0, 1, 1, 1, k_paper_primary_lean<false, 1, true, true>),
+    RT_PAP(0, 0, 0, 2, 1, 1, k_paper_primary_lean<false, 2, true, true>),
+#endif
+#endif
+};
+#undef RT_PAP
+#undef RT_STD
+#undef RT_ROW
 
-template <bool E, bool D, bool SEC, bool WV = false>
-void launch_std_c(bool c, dim3 grid, hipStream_t st, const DevScene& S, const StdParams& P) {
-    if (c) hipLaunchKernelGGL((k_std<E, D, SEC, true, WV>), grid, dim3(kStdThreads), kStdPool, st, S, P);
-    else hipLaunchKernelGGL((k_std<E, D, SEC, false, WV>), grid, dim3(kStdThreads), kStdPool, st, S, P);
+template <class P, size_t N>
+const KernelRow<P>* find_kernel(const KernelRow<P> (&table)[N], unsigned key) {
+    for (const KernelRow<P>& r : table)
+        if (r.key == key) return &r;
+    return nullptr;
 }
-
-template <bool E, bool D>
-void launch_paper_c(bool c, dim3 grid, hipStream_t st, const DevScene& S, const PaperParams& P) {
-    // (timed launches: never op-counting ones, rt_frame_trace)
-    if (c) hipLaunchKernelGGL((k_paper_primary<E, D, true>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
-    else if (P.gtime) hipLaunchKernelGGL((k_paper_primary<E, D, false, true>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
-    else hipLaunchKernelGGL((k_paper_primary<E, D, false>), pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
+// (the standard-mode kernels have no timed build, the paper ones no SEC)
+const KernelRow<StdParams>* std_row(const rtamd::KernelVariant& v) {
+    return find_kernel(kStdKernels, vkey(v.eager, v.deep, v.secondary, v.count_ops, v.wv, v.plain, false));
+}
+const KernelRow<PaperParams>* paper_row(const rtamd::KernelVariant& v) {
+    return find_kernel(kPaperKernels, vkey(v.eager, v.deep, false, v.count_ops, v.wv, v.plain, v.timed));
 }
 
 }  // namespace
 
-// Eager scenes always use D.  Each variant gets its own register allocation.
-void launch_std(bool e, bool d, bool sec, bool c, hipStream_t st, const SceneView& V, const StdParams& P) {
-    const bool bv = !e && !d && V.wave_cull && V.n_chunks > 0;
-    const DevScene S = make_scene(V, bv);
+// Each variant gets its own register allocation.  A variant this namespace
+// has no kernel for is an error, never another kernel.
+hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const SceneView& V, const StdParams& P) {
+    const KernelRow<StdParams>* k = std_row(v);
+    if (!k) return hipErrorInvalidDeviceFunction;
+    const DevScene S = make_scene(V, v.wv == 2);
     const dim3 grid((P.W + kStdBlockX - 1) / kStdBlockX, (P.n_rows + kStdBlockY - 1) / kStdBlockY);
-#ifdef RT_GENERAL_ONLY
-    // big-stack build: only the general variants (every feature, scratch stacks)
-    (void)e;
-    (void)d;
-    if (sec) launch_std_c<true, true, true>(c, grid, st, S, P);
-    else launch_std_c<true, true, false>(c, grid, st, S, P);
-#else
-    const bool wv = V.wave_cull;
-    const bool pl = V.plain != 0;
-    if (e) {
-        if (sec) launch_std_c<true, true, true>(c, grid, st, S, P);
-        else launch_std_c<true, true, false>(c, grid, st, S, P);
-    } else if (d) {
-        if (sec) launch_std_c<false, true, true>(c, grid, st, S, P);
-        else launch_std_c<false, true, false>(c, grid, st, S, P);
-    } else {
-        if (sec) {
-            if (bv) launch_secw<2>(c, pl, grid, st, S, P);
-            else if (wv) launch_secw<1>(c, pl, grid, st, S, P);
-            else launch_std_c<false, false, true>(c, grid, st, S, P);
-        } else if (bv) {
-            launch_lean<2>(c, pl, grid, st, S, P);
-        } else if (wv) {
-            launch_lean<1>(c, pl, grid, st, S, P);
-        } else {
-            launch_lean<0>(c, pl, grid, st, S, P);
-        }
-    }
-#endif
+    hipLaunchKernelGGL(k->fn, grid, dim3(kStdThreads), kStdPool, st, S, P);
+    return hipGetLastError();
 }
 
-void launch_paper(bool e, bool d, bool c, dim3 grid, hipStream_t st, const SceneView& V, const PaperParams& P) {
-    const bool bv = !e && !d && V.wave_cull && V.n_chunks > 0;
-    const DevScene S = make_scene(V, bv);
-#ifdef RT_GENERAL_ONLY
-    (void)e;
-    (void)d;
-    launch_paper_c<true, true>(c, grid, st, S, P);
-#else
-    const bool wv = V.wave_cull;
-    const bool pl = V.plain != 0;
-    if (e) launch_paper_c<true, true>(c, grid, st, S, P);
-    else if (d) launch_paper_c<false, true>(c, grid, st, S, P);
-    else if (bv) launch_paper_lean<2>(c, pl, grid, st, S, P);
-    else if (wv) launch_paper_lean<1>(c, pl, grid, st, S, P);
-    else launch_paper_lean<0>(c, pl, grid, st, S, P);
-#endif
+hipError_t launch_paper(const rtamd::KernelVariant& v, dim3 grid, hipStream_t st, const SceneView& V,
+                        const PaperParams& P) {
+    const KernelRow<PaperParams>* k = paper_row(v);
+    if (!k) return hipErrorInvalidDeviceFunction;
+    const DevScene S = make_scene(V, v.wv == 2);
+    hipLaunchKernelGGL(k->fn, pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
+    return hipGetLastError();
 }
 
-// The kernel launch_std / launch_paper pick for a variant (resource queries).
-const void* std_kernel(bool e, bool d, bool sec, bool wv, bool bv, bool pl) {
-#ifdef RT_GENERAL_ONLY
-    (void)e, (void)d, (void)wv, (void)bv, (void)pl;
-    return sec ? (const void*)k_std<true, true, true, false> : (const void*)k_std<true, true, false, false>;
-#else
-    if (e) return sec ? (const void*)k_std<true, true, true, false> : (const void*)k_std<true, true, false, false>;
-    if (d) return sec ? (const void*)k_std<false, true, true, false> : (const void*)k_std<false, true, false, false>;
-    pl = pl && kPlainKernels;
-    if (sec) {
-        if (bv) return pl ? (const void*)k_std_secw<false, 2, kPlainKernels> : (const void*)k_std_secw<false, 2>;
-        if (wv) return pl ? (const void*)k_std_secw<false, 1, kPlainKernels> : (const void*)k_std_secw<false, 1>;
-        return (const void*)k_std<false, false, true, false>;
-    }
-    if (bv) return pl ? (const void*)k_std_lean<false, 2, kPlainKernels> : (const void*)k_std_lean<false, 2>;
-    if (wv) return pl ? (const void*)k_std_lean<false, 1, kPlainKernels> : (const void*)k_std_lean<false, 1>;
-    return pl ? (const void*)k_std_lean<false, 0, kPlainKernels> : (const void*)k_std_lean<false, 0>;
-#endif
+// The kernel launch_std / launch_paper pick for a variant, and its name
+// (resource queries); {nullptr, nullptr}: none in this namespace.
+rtamd::KernelEntry std_kernel(const rtamd::KernelVariant& v) {
+    const KernelRow<StdParams>* k = std_row(v);
+    return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
+}
+rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v) {
+    const KernelRow<PaperParams>* k = paper_row(v);
+    return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
 }
 
 // The trace kernels' workgroup size and dynamic LDS (resource queries)
 int kernel_block_threads(bool paper) { return paper ? kPaperThreads : kStdThreads; }
 size_t kernel_pool_bytes(bool paper) { return paper ? kPaperPool : kStdPool; }
-
-const void* paper_kernel(bool e, bool d, bool wv, bool bv, bool pl) {
-#ifdef RT_GENERAL_ONLY
-    (void)e, (void)d, (void)wv, (void)bv, (void)pl;
-    return (const void*)k_paper_primary<true, true, false>;
-#else
-    if (e) return (const void*)k_paper_primary<true, true, false>;
-    if (d) return (const void*)k_paper_primary<false, true, false>;
-    pl = pl && kPlainKernels;
-    if (bv) return pl ? (const void*)k_paper_primary_lean<false, 2, false, kPlainKernels> : (const void*)k_paper_primary_lean<false, 2>;
-    if (wv) return pl ? (const void*)k_paper_primary_lean<false, 1, false, kPlainKernels> : (const void*)k_paper_primary_lean<false, 1>;
-    return pl ? (const void*)k_paper_primary_lean<false, 0, false, kPlainKernels> : (const void*)k_paper_primary_lean<false, 0>;
-#endif
-}
 
 void launch_paper_finish(dim3 grid, hipStream_t st, const PaperParams& P) {
     // (grid.x covers W pixels one per thread; even W: two per thread; grid.y

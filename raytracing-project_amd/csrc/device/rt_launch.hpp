@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "frame_plan.hpp"
 #include "rt.h"
 #include "scene_compile.hpp"
 
@@ -83,9 +84,7 @@ struct SceneView {
     int n_wobjs, n_chunks;
     int n_lights, n_dlights, n_objs;
     int n_bounded;
-    int wave_cull;   // wave-level culls: cull && n_bounded >= wave_cull_min() (host-decided)
     int n_lead;      // CompiledScene::n_lead (0: none / RT_LEAD=0)
-    int plain;       // only sphere / half-space / pokeball objects: the plain kernels (CntPlain, rt_device.hpp)
     int cam_nx, cam_ny;
     int rec_limit, cull;
     double eye[3], P[3], Lx, Ly;
@@ -147,43 +146,68 @@ __host__ __device__ inline double paper_code_value(unsigned code) {
     return o;
 }
 
-// Per-lane stacks of the render kernels (checked on the host per scene).
-// The common kernels carry small ones; scenes beyond them run on the
-// "big-stack" build of the general kernels (namespace rtdb,
-// rt_kernels_big.hip), whose stacks live in scratch memory.
-constexpr int kMaxRayStack = 8;   // transform nesting inside CSG operands (eager programs)
-constexpr int kMaxIvlSpill = 6;   // CSG interval stack entries beyond the top two
-constexpr int kMaxDepth = 16;     // reflection/refraction frames (medium.recursion <= 17)
-constexpr int kBigRayStack = 64;
-constexpr int kBigIvlSpill = 62;
-constexpr int kBigDepth = 128;    // medium.recursion <= 129
-
-// Scenes with at least this many bounded objects take the wave-level culling
-// kernels (WV >= 1).  RT_WV_MIN overrides it (measurement A/B; default 4).
-int wave_cull_min();
-
 constexpr int kCounterWords = 2 + 16;   // isect, occl, ops[16]
 constexpr int kCounterSlots = 512;      // spread of the per-block counter atomics
 
+// A trace kernel (its host handle) and its name as rocprofv3 prints it,
+// without the namespace (e.g. "k_std_lean<false, 1, false>")
+struct KernelEntry {
+    const void* fn;
+    const char* name;
+};
+
 }  // namespace rtamd
 
-// Kernel variants (rt_kernels.hpp): E = scene has eager (transform-inside-CSG)
-// objects, D = general compact CSG (deep stacks, directional lights),
-// SEC = reflection/refraction frames, C = op counting, pl = plain scene
-// (SceneView::plain: the lean / recursion / paper kernels without transform
-// and CSG code).
+// The trace kernels of one namespace (rt_kernels.hpp), by KernelVariant
+// (frame_plan.hpp).  launch_*: hipErrorInvalidDeviceFunction when the
+// namespace has no kernel for the variant.
 #define RT_DECLARE_LAUNCHERS(NS)                                                                                  \
     namespace NS {                                                                                                \
-    void launch_std(bool e, bool d, bool sec, bool c, hipStream_t st, const rtamd::SceneView& V,                 \
-                    const rtamd::StdParams& P);                                                                   \
-    void launch_paper(bool e, bool d, bool c, dim3 grid, hipStream_t st, const rtamd::SceneView& V,               \
-                      const rtamd::PaperParams& P);                                                               \
+    hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,               \
+                          const rtamd::StdParams& P);                                                             \
+    hipError_t launch_paper(const rtamd::KernelVariant& v, dim3 grid, hipStream_t st, const rtamd::SceneView& V,  \
+                            const rtamd::PaperParams& P);                                                         \
     void launch_paper_finish(dim3 grid, hipStream_t st, const rtamd::PaperParams& P);                             \
-    const void* std_kernel(bool e, bool d, bool sec, bool wv, bool bv, bool pl);                                  \
-    const void* paper_kernel(bool e, bool d, bool wv, bool bv, bool pl);                                          \
+    rtamd::KernelEntry std_kernel(const rtamd::KernelVariant& v);                                                 \
+    rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v);                                               \
     int kernel_block_threads(bool paper);                                                                         \
     size_t kernel_pool_bytes(bool paper);                                                                         \
     }
 RT_DECLARE_LAUNCHERS(rtd)
 RT_DECLARE_LAUNCHERS(rtf)
 RT_DECLARE_LAUNCHERS(rtdb)
+
+// The launchers of a variant's namespace (the big-stack build has no finish
+// pass of its own: k_paper_finish reads records only).
+namespace rtamd {
+inline hipError_t launch_std(const KernelVariant& v, hipStream_t st, const SceneView& V, const StdParams& P) {
+    return v.ns == KernelVariant::kRtf ? rtf::launch_std(v, st, V, P)
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_std(v, st, V, P) : rtd::launch_std(v, st, V, P);
+}
+inline hipError_t launch_paper(const KernelVariant& v, dim3 grid, hipStream_t st, const SceneView& V,
+                               const PaperParams& P) {
+    return v.ns == KernelVariant::kRtf ? rtf::launch_paper(v, grid, st, V, P)
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_paper(v, grid, st, V, P)
+                                                                      : rtd::launch_paper(v, grid, st, V, P);
+}
+inline void launch_paper_finish(const KernelVariant& v, dim3 grid, hipStream_t st, const PaperParams& P) {
+    if (v.ns == KernelVariant::kRtf) rtf::launch_paper_finish(grid, st, P);
+    else rtd::launch_paper_finish(grid, st, P);
+}
+// The variant's trace kernel of `mode` ({nullptr, nullptr}: none), and its launch shape
+inline KernelEntry trace_kernel(const KernelVariant& v, bool paper) {
+    if (v.ns == KernelVariant::kRtf) return paper ? rtf::paper_kernel(v) : rtf::std_kernel(v);
+    if (v.ns == KernelVariant::kRtdb) return paper ? rtdb::paper_kernel(v) : rtdb::std_kernel(v);
+    return paper ? rtd::paper_kernel(v) : rtd::std_kernel(v);
+}
+inline int trace_block_threads(const KernelVariant& v, bool paper) {
+    return v.ns == KernelVariant::kRtf ? rtf::kernel_block_threads(paper)
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::kernel_block_threads(paper)
+                                                                      : rtd::kernel_block_threads(paper);
+}
+inline size_t trace_pool_bytes(const KernelVariant& v, bool paper) {
+    return v.ns == KernelVariant::kRtf ? rtf::kernel_pool_bytes(paper)
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::kernel_pool_bytes(paper)
+                                                                      : rtd::kernel_pool_bytes(paper);
+}
+}  // namespace rtamd

@@ -9,6 +9,10 @@
 //   trace_paper, the centre probe and the four neighbour probes of
 //   get_edge_strength, which all re-trace identical rays) + shading.
 //   k_paper_finish: edge strength from the stored neighbour hits + hatch.
+// What a frame launches and over which rows is decided in host-only code
+// (csrc/host/frame_plan.hpp: pick_variant, plan_std_frame, plan_paper_frame,
+// PaperCalls); rt_frame_begin / trace / end here execute that plan.  The
+// rt_test_* hooks live in rt_test_hooks.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -28,29 +32,15 @@
 #include "pinned.hpp"
 #include "mt_poly.hpp"
 #include "rt.h"
+#include "rt_devbuf.hpp"
 #include "rt_launch.hpp"
 #include "rt_internal.hpp"
 #include "scene_compile.hpp"
 
 using rtamd::kCounterSlots;
-using rtamd::kMaxDepth;
-using rtamd::kMaxIvlSpill;
-using rtamd::kMaxRayStack;
 using rtamd::kCounterWords;
 using rtamd::PaperParams;
 using rtamd::SceneView;
-
-namespace {
-// SceneView::plain: every object a sphere, half-space or pokeball (no
-// transform or CSG object: the plain kernels, rt_device.hpp CntPlain)
-bool plain_scene(const rtamd::CompiledScene& cs) {
-    for (const auto& o : cs.objs)
-        if (o.kind != rtamd::OBJ_SPHERE && o.kind != rtamd::OBJ_HALF && o.kind != rtamd::OBJ_POKE &&
-            o.kind != rtamd::OBJ_NEVER && o.kind != rtamd::OBJ_GROUP)
-            return false;
-    return true;
-}
-}  // namespace
 using rtamd::StdParams;
 
 namespace {
@@ -111,38 +101,7 @@ __global__ void __launch_bounds__(64) k_reduce_counters(unsigned long long* __re
 }
 
 // ------------------------------------------------------------ host side
-#define HIP_TRY(expr)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) {                                                                  \
-            rtamd::set_last_error(std::string(#expr) + " failed: " + hipGetErrorString(e_));     \
-            return RT_ERR_HIP;                                                                   \
-        }                                                                                        \
-    } while (0)
-
-// Growable device buffer.
-struct DBuf {
-    void* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        rtamd::SetupTimer tm(rtamd::kSetupAlloc);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
+using DBuf = rtamd::DevBufT<8>;   // (growth slack 1/8)
 
 // The device-resident copy of one scene (compiled object table + records in
 // the launching precision).  A scene handle is immutable, so the copy is
@@ -199,9 +158,8 @@ struct Workspace {
     // paper mode: measured primary-pass cost of each 8-entry list group of a
     // frame, by the group's first ext index, per frame key (scene, size,
     // mode, flags, rows): the next frame of that key launches its groups
-    // costliest first (order_paper_groups)
+    // costliest first (frame_plan.hpp order_paper_groups)
     std::map<uint64_t, std::vector<uint32_t>> paper_cost;
-    std::vector<rtamd::JRange> jranges;
     std::vector<int32_t> rows_cached;   // what `rows` holds (a frame with the same rows skips the upload)
     bool counters_zero = false;         // the last frame's k_reduce_counters left `counters` zero (no memset)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -266,26 +224,15 @@ struct rt_frame {
     hipStream_t st = nullptr;
     SceneView S;
     int W = 0, H = 0, mode = 0, n_rows = 0;
-    bool eager = false, deep = false, secondary = false, count_ops = false, fp32 = false;
-    bool big = false;                          // big-stack kernels (rtdb)
-    bool traced = false;
+    rtamd::KernelVariant kv;                   // the frame's trace kernel (frame_plan.hpp pick_variant)
+    bool fp32 = false;
     bool timed = false;                        // paper mode: a launch stored its waves' ticks (PaperParams::gtime)
     int bvh_trial = -1;                        // SceneCache::bvh_trial this frame measures (-1: none)
-    std::vector<int32_t> rows;
-    std::vector<int32_t> rows_jrow;            // standard mode: rows | jitter row of each
     std::chrono::steady_clock::time_point t_start;
-    uint64_t logical_isect = 0;
-    // paper mode: ext = rendered rows and their vertical neighbours
-    int n_ext = 0;
-    std::vector<int32_t> ext_pos;              // output row -> ext index (-1: none)
-    std::vector<int> ext_done;                 // primary hit launched by trace call (value - 1); 0 = not yet
-    std::vector<hipStream_t> call_st;          // stream of each trace call
-    int list_used = 0;                         // ext-list entries consumed in the aux buffer (a multiple of 16)
-    uint64_t key = 0;                          // paper mode: Workspace::paper_cost key
-    std::vector<std::pair<int, int>> calls;    // paper mode: (list offset, f->stage index) of each launched list
-    int n_tev = 0;                             // trace events recorded (ws.tev[0 .. n_tev))
-    hipStream_t last_st = nullptr;             // stream of the previous trace call
-    std::vector<std::vector<int32_t>> stage;   // host sources of async uploads
+    rtamd::StdPlan std_plan;                   // standard mode (host source of the rows upload)
+    rtamd::PaperPlan paper;                    // paper mode (host source of the aux upload)
+    rtamd::PaperCalls paper_calls;             //   its trace calls' lists (host sources of their uploads)
+    std::vector<hipStream_t> call_st;          // stream of each trace call (ws.tev[i] its end)
 };
 
 namespace {
@@ -340,64 +287,6 @@ void make_float_scene(SceneCache& f) {
         f.fold_f[i].pc = f.cs.fold[i].pc;
         f.fold_f[i].pad = 0;
     }
-}
-
-// Paper mode launch order.  A wave of k_paper_primary covers one 8-entry
-// group of the ext list; a group's cost varies ~10x over a frame (sky rows
-// against crowded ones, profiles/r04s_strips5.json).  Launched in row order,
-// the costly rows of the lower frame start last and their waves form the
-// launch's tail: one launch of a rank's rows of an 8-way config-5 frame took
-// 0.858 ms in row order, 0.799 ms costliest strips first, 0.994 ms cheapest
-// first (profiles/r04y_order5.jsonl).  So every primary wave stores its
-// start and end ticks (PaperParams::gtime), rt_frame_end sums them per group
-// and keeps them per frame key, and the next frame of that key launches its
-// 16-entry blocks (workgroup rows) costliest first.  Measured: one GPU
-// 5.37 -> 5.33 ms, the slowest of 8 ranks' trace 0.95 -> 0.93 ms
-// (profiles/r04_ab/ab_order.jsonl).  Groups keep their entries (each wave
-// stays on 8 consecutive rows of one strip); only the launch order changes,
-// which no pixel depends on.  A frame with no history runs in row order.
-// primary waves per 8-entry list group (k_paper_primary: 16-column blocks of 2x2 waves)
-int paper_waves_per_group(int W) { return 2 * ((W + 15) / 16); }
-
-uint64_t paper_frame_key(uint64_t uid, int W, int H, int mode, int flags, const int32_t* rows, int n_rows) {
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&h](uint64_t v) {
-        for (int i = 0; i < 8; ++i) {
-            h ^= (v >> (8 * i)) & 0xff;
-            h *= 1099511628211ull;
-        }
-    };
-    mix(uid);
-    mix((uint64_t)(uint32_t)W << 32 | (uint32_t)H);
-    mix((uint64_t)(uint32_t)mode << 32 | (uint32_t)flags);
-    mix((uint64_t)n_rows);
-    for (int i = 0; i < n_rows; ++i) mix((uint64_t)(uint32_t)rows[i]);
-    return h;
-}
-
-// Reorders the 16-entry blocks of list (one workgroup row: its four waves
-// share the workgroup's culls, so a block stays one piece) costliest first
-// when every 8-entry group with an entry has a measured cost (else leaves the
-// row order); padding blocks go last.
-void order_paper_groups(std::vector<int32_t>& list, const std::vector<uint32_t>* cost) {
-    if (!cost) return;
-    const size_t nb = list.size() / 16;
-    std::vector<std::pair<uint64_t, size_t>> key(nb);
-    for (size_t b = 0; b < nb; ++b) {
-        uint64_t c = 0;
-        for (size_t g = 2 * b; g < 2 * b + 2; ++g) {
-            int32_t e = -1;
-            for (size_t i = 0; i < 8 && e < 0; ++i) e = list[8 * g + i];
-            if (e < 0) continue;
-            if ((size_t)e >= cost->size() || (*cost)[e] == 0) return;   // not measured: row order
-            c += (*cost)[e];
-        }
-        key[b] = {c, b};
-    }
-    std::stable_sort(key.begin(), key.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-    std::vector<int32_t> out(list.size());
-    for (size_t j = 0; j < nb; ++j) std::copy_n(list.begin() + 16 * key[j].second, 16, out.begin() + 16 * j);
-    list.swap(out);
 }
 
 int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int32_t* rows_host, int n_rows,
@@ -508,44 +397,12 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
         sc.bvh_key = 0;
     }
     const rtamd::CompiledScene& cs = sc.cs;
-    bool secondary = false;
-    for (int i = 0; i < d.n_materials; ++i)
-        if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) secondary = true;
-    if (d.recursion_limit < 2) secondary = false;   // depth < limit-1 never holds (tracer.cpp:38,51)
-    // Stack tiers: the common kernels, else the big-stack build (rtdb), else refuse.
-    const int frames = (secondary && mode == RT_MODE_STANDARD) ? d.recursion_limit - 1 : 0;
-    bool big = false;
-    if (cs.max_ray_depth > kMaxRayStack || cs.max_ivl_depth > kMaxIvlSpill + 2 || frames > kMaxDepth) {
-        if (cs.max_ray_depth > rtamd::kBigRayStack || cs.max_ivl_depth > rtamd::kBigIvlSpill + 2 ||
-            frames > rtamd::kBigDepth) {
-            rtamd::set_last_error("scene exceeds the device stacks: transform nesting inside CSG operands " +
-                                  std::to_string(cs.max_ray_depth) + " (max " + std::to_string(rtamd::kBigRayStack) +
-                                  "), CSG operand depth " + std::to_string(cs.max_ivl_depth) + " (max " +
-                                  std::to_string(rtamd::kBigIvlSpill + 2) + "), medium.recursion " +
-                                  std::to_string(d.recursion_limit) + " with reflection/refraction (max " +
-                                  std::to_string(rtamd::kBigDepth + 1) + ")");
-            return RT_ERR_UNSUPPORTED;
-        }
-        if (fp32) {
-            rtamd::set_last_error("the FP32 fast path has only the common device stacks; render this scene in FP64");
-            return RT_ERR_UNSUPPORTED;
-        }
-        big = true;
-    }
     f->st = st;
     f->W = W;
     f->H = H;
     f->mode = mode;
     f->n_rows = n_rows;
-    f->eager = cs.has_eager;
-    // the lean kernels carry no directional-light code: such scenes take the
-    // general (D) variants
-    f->deep = cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
-    f->secondary = secondary;
-    f->count_ops = (flags & RT_FLAG_COUNT_OPS) != 0;
     f->fp32 = fp32;
-    f->big = big;
-    f->rows.assign(rows_host, rows_host + n_rows);
     f->t_start = t_start;
     if (!ws.ev[0]) {
         rtamd::SetupTimer tm(rtamd::kSetupStreams);
@@ -600,12 +457,15 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
     S.cam_ny = rt_camera_height(&d.camera);
     S.rec_limit = d.recursion_limit;
     S.cull = (flags & RT_FLAG_NO_CULL) ? 0 : 1;
-    S.wave_cull = S.cull && S.n_bounded >= rtamd::wave_cull_min();
     {
         static const bool lead_on = [] { const char* e = std::getenv("RT_LEAD"); return !(e && *e == '0'); }();
         S.n_lead = lead_on ? cs.n_lead : 0;   // (RT_LEAD=0: measurement A/B)
-        static const bool plain_on = [] { const char* e = std::getenv("RT_PLAIN"); return !(e && *e == '0'); }();
-        S.plain = plain_on && plain_scene(cs) ? 1 : 0;   // (RT_PLAIN=0: measurement A/B)
+    }
+    // the trace kernel (the stack tiers, the culling and plain variants);
+    // this frame's BVH trial may run it without the wave BVH
+    {
+        const int rv = rtamd::pick_variant(cs, d, mode, flags, S.n_chunks > 0, &f->kv);
+        if (rv != RT_OK) return rv;
     }
     for (int i = 0; i < 3; ++i) {
         S.eye[i] = d.camera.eye[i];
@@ -617,16 +477,13 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
     S.bg_mat = d.n_materials;
 
     if (n_rows > 0 && mode == RT_MODE_STANDARD) {
+        f->std_plan = rtamd::plan_std_frame(W, H, rows_host, n_rows, (int64_t)rtamd::kTableK * 624);
         // the checkpoint table must reach the last loop row's stream words
         // (built on the first frame, extended only for a larger frame)
-        int max_y = 0;
-        for (int i = 0; i < n_rows; ++i) max_y = std::max(max_y, H - 1 - rows_host[i]);
-        const int64_t q_end = (int64_t)32 * W * (max_y + 1);
         try {   // (the jump polynomials: file read or GF(2) arithmetic, may throw)
-            const int64_t n_need = (q_end - 1) / ((int64_t)rtamd::kTableK * 624) + 1;
-            if (n_need > ws.jtab.n_ck) {   // a build or an extension: synchronous
+            if (f->std_plan.n_ckpt > ws.jtab.n_ck) {   // a build or an extension: synchronous
                 const auto t_j = SClock::now();
-                HIP_TRY(ws.jtab.ensure(n_need, st));
+                HIP_TRY(ws.jtab.ensure(f->std_plan.n_ckpt, st));
                 std::lock_guard<std::mutex> lk(g_setup.mu);
                 g_setup.jtable_ms += ms_since(t_j);
             }
@@ -637,89 +494,31 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
     }
     HIP_TRY(hipEventRecord(ws.ev[0], st));
     if (n_rows > 0 && mode == RT_MODE_STANDARD) {
-        // Loop row y = H-1-rows[ri] consumes outputs [32Wy, 32W(y+1))
-        // (tracer.cpp:284-293).  Jitter rows are laid out in stream order
-        // (jrow = rank of y), so runs of consecutive loop rows - a strip, or
-        // the whole frame - are one range for the generator.
-        const int64_t row_q = (int64_t)32 * W;
-        std::vector<int32_t> order(n_rows);
-        for (int ri = 0; ri < n_rows; ++ri) order[ri] = ri;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return f->rows[a] > f->rows[b]; });
-        f->rows_jrow.assign(f->rows.begin(), f->rows.end());
-        f->rows_jrow.resize(2 * (size_t)n_rows);
-        ws.jranges.clear();
-        for (int k = 0; k < n_rows; ++k) {
-            const int ri = order[k];
-            f->rows_jrow[n_rows + ri] = k;
-            const int64_t y = H - 1 - f->rows[ri];
-            if (!ws.jranges.empty() && ws.jranges.back().qb == row_q * y)
-                ws.jranges.back().qb += row_q;
-            else
-                ws.jranges.push_back(rtamd::JRange{row_q * y, row_q * (y + 1), (int64_t)k * 16 * W});
-        }
-        const int64_t q1 = ws.jranges.back().qb;
+        const rtamd::StdPlan& sp = f->std_plan;
         HIP_TRY(ws.jit.ensure((size_t)n_rows * 16 * W * sizeof(double)));
-        HIP_TRY(ws.jscratch.ensure(rtamd::mt_fill_scratch_bytes(ws.jranges)));
+        HIP_TRY(ws.jscratch.ensure(rtamd::mt_fill_scratch_bytes(sp.jranges)));
         // (the rows / jitter-row lists of the previous frame of this
         // workspace are still on the device: the same row set skips the copy)
-        if (!(ws.rows.p && ws.rows_cached == f->rows_jrow)) {
-            HIP_TRY(upload(ws.rows, f->rows_jrow, st, &ws.up));
-            ws.rows_cached = f->rows_jrow;
+        if (!(ws.rows.p && ws.rows_cached == sp.rows_jrow)) {
+            HIP_TRY(upload(ws.rows, sp.rows_jrow, st, &ws.up));
+            ws.rows_cached = sp.rows_jrow;
         }
         ws.jjob.up = &ws.up;
         const auto t_l = SClock::now();
-        HIP_TRY(rtamd::mt_launch_fill(ws.jtab, ws.jranges, ws.jjob, ws.jscratch.p, ws.jit.as<double>(), st));
+        HIP_TRY(rtamd::mt_launch_fill(ws.jtab, sp.jranges, ws.jjob, ws.jscratch.p, ws.jit.as<double>(), st));
         {
             std::lock_guard<std::mutex> lk(g_setup.mu);
             if (!g_setup.jitter_launched) g_setup.jitter_launch_ms = ms_since(t_l);
             g_setup.jitter_launched = true;
         }
-        (void)q1;
     } else if (n_rows > 0) {
-        // rows needing a primary hit: rendered rows and their vertical neighbours
-        std::vector<char> need(H, 0), shade_row(H, 0);
-        for (int r : f->rows) {
-            need[r] = 1;
-            shade_row[r] = 1;
-            if (r > 0) need[r - 1] = 1;
-            if (r + 1 < H) need[r + 1] = 1;
-        }
-        std::vector<int32_t> ext, ext_shade;
-        f->ext_pos.assign(H, -1);
-        for (int r = 0; r < H; ++r)
-            if (need[r]) {
-                f->ext_pos[r] = (int)ext.size();
-                ext.push_back(r);
-                ext_shade.push_back(shade_row[r]);
-            }
-        std::vector<int32_t> nbr(3 * (size_t)n_rows);
-        for (int i = 0; i < n_rows; ++i) {
-            const int r = f->rows[i];
-            nbr[3 * i + 0] = r > 0 ? f->ext_pos[r - 1] : -1;
-            nbr[3 * i + 1] = f->ext_pos[r];
-            nbr[3 * i + 2] = r + 1 < H ? f->ext_pos[r + 1] : -1;
-            // logical Scene::intersect calls: trace_paper + centre + valid neighbours
-            f->logical_isect += (uint64_t)W * 2 + (uint64_t)(W > 1 ? 2 * (W - 1) : 0) +
-                                (uint64_t)W * ((r > 0) + (r + 1 < H));
-        }
-        f->n_ext = (int)ext.size();
-        f->ext_done.assign(f->n_ext, 0);
-        // aux: ext_rows | ext_shade | nbr | rows | ext lists (n_ext, filled per trace call)
-        f->stage.emplace_back();
-        std::vector<int32_t>& ints = f->stage.back();
-        ints.insert(ints.end(), ext.begin(), ext.end());
-        ints.insert(ints.end(), ext_shade.begin(), ext_shade.end());
-        ints.insert(ints.end(), nbr.begin(), nbr.end());
-        ints.insert(ints.end(), f->rows.begin(), f->rows.end());
-        // (+ the ext lists of the trace calls: every entry once, each run padded
-        // by < 8 to a group boundary and each call's list by < 16 to a block)
-        HIP_TRY(ws.paper_aux.ensure((ints.size() + 24 * (size_t)f->n_ext) * sizeof(int32_t)));
-        f->key = paper_frame_key(rtamd::scene_uid(s), W, H, mode, flags, rows_host, n_rows);
-        // primary waves' (start, end) ticks: <= 3 list groups per ext row (the
-        // list capacity / 8), 2 * ceil(W / 16) waves per group
-        HIP_TRY(ws.gtime.ensure((size_t)3 * f->n_ext * paper_waves_per_group(W) * 2 * sizeof(unsigned)));
-        HIP_TRY(rtamd::upload_async(&ws.up, ws.paper_aux.p, ints.data(), ints.size() * sizeof(int32_t), st));
-        const size_t npx = (size_t)f->n_ext * W;
+        f->paper = rtamd::plan_paper_frame(rtamd::scene_uid(s), W, H, mode, flags, rows_host, n_rows);
+        f->paper_calls.reset(&f->paper);
+        const rtamd::PaperPlan& pp = f->paper;
+        HIP_TRY(ws.paper_aux.ensure(pp.aux_ints() * sizeof(int32_t)));
+        HIP_TRY(ws.gtime.ensure(pp.gtime_words() * sizeof(unsigned)));
+        HIP_TRY(rtamd::upload_async(&ws.up, ws.paper_aux.p, pp.aux.data(), pp.aux.size() * sizeof(int32_t), st));
+        const size_t npx = (size_t)pp.n_ext * W;
         HIP_TRY(ws.paper_i.ensure(npx * sizeof(int)));
         HIP_TRY(ws.paper_d.ensure(npx * 4 * sizeof(double)));
     }
@@ -752,39 +551,21 @@ int frame_trace(rt_frame* f, int ri0, int ri1, double* fb, hipStream_t hs, uint8
     // another stream first waits for the scene upload and jitter (begin).  In
     // paper mode a chunk whose finish pass reads primary hits that an earlier
     // call computed on another stream waits for that call's PRIMARY pass
-    // (adjacent strips share a neighbour row: one GPU's chunked frame, or
-    // adjacent strips of one rank), and only its finish waits: its primary
-    // computes new entries only, so it overlaps the earlier call's finish
-    // (latency-bound) on the other stream.
+    // (PaperCalls::next_call: one GPU's chunked frame, or adjacent strips of
+    // one rank), and only its finish waits: its primary computes new entries
+    // only, so it overlaps the earlier call's finish (latency-bound) on the
+    // other stream.
     const auto t_launch = SClock::now();
     if (st != f->st) HIP_TRY(hipStreamWaitEvent(st, ws.ev[1], 0));
-    std::vector<char> wait;
-    if (f->mode == RT_MODE_PAPER && f->n_tev > 0) {
-        wait.assign(f->n_tev, 0);
-        for (int i = ri0; i < ri1; ++i) {
-            const int r = f->rows[i];
-            for (int rr = r - 1; rr <= r + 1; ++rr) {
-                if (rr < 0 || rr >= f->H) continue;
-                const int e = f->ext_pos[rr];
-                if (e >= 0 && f->ext_done[e]) {
-                    const int c = f->ext_done[e] - 1;   // the call that computed it
-                    if (f->call_st[c] != st) wait[c] = 1;
-                }
-            }
+    const int call = (int)f->call_st.size();   // this call's index (ws.pev / ws.tev)
+    // paper mode: a call that fails before its events are recorded is taken
+    // back, so that a later call never waits on an event that was not recorded
+    struct Rollback {
+        rtamd::PaperCalls* calls;
+        ~Rollback() {
+            if (calls) calls->rollback();
         }
-    }
-    // paper mode: the ext entries this call marks as its own (ext_done) are
-    // unmarked again if the call fails before its event is recorded, so that a
-    // later call never waits on an event that was not recorded
-    struct Unmark {
-        std::vector<int>& done;
-        std::vector<int32_t> marked;
-        bool keep = false;
-        ~Unmark() {
-            if (!keep)
-                for (int32_t e : marked) done[e] = 0;
-        }
-    } unmark{f->ext_done, {}};
+    } undo{nullptr};
     if (f->mode == RT_MODE_STANDARD) {
         StdParams P;
         P.W = W;
@@ -795,48 +576,39 @@ int frame_trace(rt_frame* f, int ri0, int ri1, double* fb, hipStream_t hs, uint8
         P.jit = ws.jit.as<double>();
         P.fb = fb;
         P.counters = ctr;
-        if (f->fp32) rtf::launch_std(f->eager, f->deep, f->secondary, f->count_ops, st, f->S, P);
-        else if (f->big) rtdb::launch_std(true, true, f->secondary, f->count_ops, st, f->S, P);
-        else rtd::launch_std(f->eager, f->deep, f->secondary, f->count_ops, st, f->S, P);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(rtamd::launch_std(f->kv, st, f->S, P));
     } else {
-        // primary hits of the ext rows this chunk reads that no earlier chunk
-        // computed.  k_paper_primary's waves are 8 list entries tall: each run
-        // of consecutive rows starts on a wave boundary (entries -1 pad), so no
-        // wave mixes rows of different strips (the wave-level culls need
-        // coherent rays).
-        std::vector<int32_t> list;
-        int prev_row = -2;
-        for (int i = ri0; i < ri1; ++i) {
-            const int r = f->rows[i];
-            for (int rr = r - 1; rr <= r + 1; ++rr) {
-                if (rr < 0 || rr >= f->H) continue;
-                const int e = f->ext_pos[rr];
-                if (e >= 0 && !f->ext_done[e]) {
-                    f->ext_done[e] = f->n_tev + 1;   // (this call's index + 1)
-                    unmark.marked.push_back(e);
-                    if (rr != prev_row + 1)
-                        while (list.size() % 8) list.push_back(-1);
-                    list.push_back(e);
-                    prev_row = rr;
-                }
-            }
+        // RT_PAPER_ORDER (measurement A/B): 0 = row order, untimed; 1 = row
+        // order, every frame timed; 2 (default) = costliest blocks first,
+        // from the wave times of the first frame of the scene and row set
+        // (later frames untimed: a timed launch reads the clock ahead of
+        // the scene loads, which costs it its scalar loads, k_paper_primary_lean)
+        static const int order_mode = [] { const char* e = std::getenv("RT_PAPER_ORDER"); return e && *e ? std::atoi(e) : 2; }();
+        const rtamd::PaperPlan& pp = f->paper;
+        const auto cost_it = ws.paper_cost.find(pp.key);
+        const bool have_cost = cost_it != ws.paper_cost.end();
+        // primary hits of the ext rows this chunk reads that no earlier chunk computed
+        const rtamd::PaperCalls::Call c = f->paper_calls.next_call(
+            ri0, ri1, reinterpret_cast<uintptr_t>(st), order_mode >= 2 && have_cost ? &cost_it->second : nullptr);
+        if (!c.ok) {
+            rtamd::set_last_error("rt_frame_trace: paper-mode list overflow");
+            return RT_ERR_PROCESSING;
         }
-        const int32_t* aux = ws.paper_aux.as<int32_t>();
-        const int n_ext = f->n_ext, n_rows = f->n_rows;
+        undo.calls = &f->paper_calls;
+        int32_t* aux = ws.paper_aux.as<int32_t>();
         PaperParams P;
         P.W = W;
         P.H = f->H;
-        P.n_ext = n_ext;
-        P.ext_rows = aux;
-        P.ext_shade = aux + n_ext;
-        P.nbr = aux + 2 * n_ext + 3 * (size_t)ri0;
-        P.rows = aux + 2 * n_ext + 3 * (size_t)n_rows + ri0;
-        int32_t* d_list = ws.paper_aux.as<int32_t>() + 2 * n_ext + 4 * (size_t)n_rows + f->list_used;
+        P.n_ext = pp.n_ext;
+        P.ext_rows = aux + pp.off_ext_rows();
+        P.ext_shade = aux + pp.off_ext_shade();
+        P.nbr = aux + pp.off_nbr() + 3 * (size_t)ri0;
+        P.rows = aux + pp.off_rows() + ri0;
+        int32_t* d_list = aux + pp.off_lists() + c.list_off;
         P.ext_list = d_list;
-        P.n_list = (int)list.size();
+        P.n_list = (int)c.list->size();
         P.n_rows = n;
-        const size_t npx = (size_t)n_ext * W;
+        const size_t npx = (size_t)pp.n_ext * W;
         P.mat = ws.paper_i.as<int>();
         double* dd = ws.paper_d.as<double>();
         P.t = dd;
@@ -847,48 +619,25 @@ int frame_trace(rt_frame* f, int ri0, int ri1, double* fb, hipStream_t hs, uint8
         P.code = codes;
         P.gtime = nullptr;
         P.counters = ctr;
-        if (!list.empty()) {
-            while (list.size() % 16) list.push_back(-1);   // whole blocks: the group index is li / 8
-            if ((size_t)f->list_used + list.size() > 24 * (size_t)n_ext) {
-                rtamd::set_last_error("rt_frame_trace: paper-mode list overflow");
-                return RT_ERR_PROCESSING;
+        if (!c.list->empty()) {
+            rtamd::KernelVariant kv = f->kv;
+            if (!kv.count_ops && (order_mode == 1 || (order_mode >= 2 && !have_cost))) {
+                P.gtime = ws.gtime.as<unsigned>() + (size_t)(c.list_off / 8) * rtamd::paper_waves_per_group(W) * 2;
+                kv.timed = f->timed = true;
             }
-            // RT_PAPER_ORDER (measurement A/B): 0 = row order, untimed; 1 = row
-            // order, every frame timed; 2 (default) = costliest blocks first,
-            // from the wave times of the first frame of the scene and row set
-            // (later frames untimed: a timed launch reads the clock ahead of
-            // the scene loads, which costs it its scalar loads, k_paper_primary_lean)
-            static const int order_mode = [] { const char* e = std::getenv("RT_PAPER_ORDER"); return e && *e ? std::atoi(e) : 2; }();
-            const auto cost_it = ws.paper_cost.find(f->key);
-            const bool have_cost = cost_it != ws.paper_cost.end();
-            if (order_mode >= 2) order_paper_groups(list, have_cost ? &cost_it->second : nullptr);
-            P.n_list = (int)list.size();
-            if (!f->count_ops && (order_mode == 1 || (order_mode >= 2 && !have_cost))) {
-                P.gtime = ws.gtime.as<unsigned>() + (size_t)(f->list_used / 8) * paper_waves_per_group(W) * 2;
-                f->timed = true;
-            }
-            f->calls.emplace_back(f->list_used, (int)f->stage.size());
-            f->list_used += (int)list.size();
-            f->stage.push_back(std::move(list));
-            const std::vector<int32_t>& L = f->stage.back();
-            HIP_TRY(rtamd::upload_async(&ws.up, d_list, L.data(), L.size() * sizeof(int32_t), st));
+            HIP_TRY(rtamd::upload_async(&ws.up, d_list, c.list->data(), c.list->size() * sizeof(int32_t), st));
             dim3 g1((W + 15) / 16, (P.n_list + 15) / 16);
-            if (f->fp32) rtf::launch_paper(f->eager, f->deep, f->count_ops, g1, st, f->S, P);
-            else if (f->big) rtdb::launch_paper(true, true, f->count_ops, g1, st, f->S, P);
-            else rtd::launch_paper(f->eager, f->deep, f->count_ops, g1, st, f->S, P);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(rtamd::launch_paper(kv, g1, st, f->S, P));
         }
-        if ((int)ws.pev.size() <= f->n_tev) {
+        if ((int)ws.pev.size() <= call) {
             hipEvent_t e = nullptr;
             HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             ws.pev.push_back(e);
         }
-        HIP_TRY(hipEventRecord(ws.pev[f->n_tev], st));
-        for (size_t c = 0; c < wait.size(); ++c)
-            if (wait[c]) HIP_TRY(hipStreamWaitEvent(st, ws.pev[c], 0));
+        HIP_TRY(hipEventRecord(ws.pev[call], st));
+        for (int w : c.wait) HIP_TRY(hipStreamWaitEvent(st, ws.pev[w], 0));
         dim3 g2((W + 63) / 64, (n + 3) / 4);
-        if (f->fp32) rtf::launch_paper_finish(g2, st, P);
-        else rtd::launch_paper_finish(g2, st, P);
+        rtamd::launch_paper_finish(f->kv, g2, st, P);
         HIP_TRY(hipGetLastError());
     }
     {
@@ -896,19 +645,16 @@ int frame_trace(rt_frame* f, int ri0, int ri1, double* fb, hipStream_t hs, uint8
         if (!g_setup.trace_launched) g_setup.trace_launch_ms = ms_since(t_launch);
         g_setup.trace_launched = true;
     }
-    if ((int)ws.tev.size() <= f->n_tev) {
+    if ((int)ws.tev.size() <= call) {
         hipEvent_t e = nullptr;
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ws.tev.push_back(e);
     }
-    HIP_TRY(hipEventRecord(ws.tev[f->n_tev], st));
+    HIP_TRY(hipEventRecord(ws.tev[call], st));
     rtamd::note_setup_ms(rtamd::kLastTrace, ms_since(t_launch));
     HIP_TRY(rtamd::warm_copy_engine(st));   // (once per process, while the trace runs)
-    unmark.keep = true;
+    undo.calls = nullptr;
     f->call_st.push_back(st);
-    ++f->n_tev;
-    f->last_st = st;
-    f->traced = true;
     return RT_OK;
 }
 
@@ -935,14 +681,14 @@ int frame_end_body(rt_frame* f, rt_stats* stats) {
     const hipStream_t st = f->st;
     // join the other trace streams: one wait on each one's last call (stream
     // order covers its earlier ones; every wait is a barrier packet on st)
-    for (int i = 0; i < f->n_tev; ++i) {
+    for (size_t i = 0; i < f->call_st.size(); ++i) {
         if (f->call_st[i] == st) continue;
         bool last = true;
-        for (int j = i + 1; j < f->n_tev; ++j) last = last && f->call_st[j] != f->call_st[i];
+        for (size_t j = i + 1; j < f->call_st.size(); ++j) last = last && f->call_st[j] != f->call_st[i];
         if (last) HIP_TRY(hipStreamWaitEvent(st, ws.tev[i], 0));
     }
     HIP_TRY(hipEventRecord(ws.ev[2], st));
-    const int n_groups = f->list_used / 8;
+    const int n_groups = f->paper_calls.list_used() / 8;
     const size_t host_words = kCounterWords + ((size_t)n_groups + 1) / 2;
     if (!ws.ctr_host || ws.ctr_host_words < host_words) {
         if (ws.ctr_host) (void)hipHostFree(ws.ctr_host);   // (the previous frame's readback is done)
@@ -956,7 +702,7 @@ int frame_end_body(rt_frame* f, rt_stats* stats) {
     unsigned long long* ctr = ws.counters.as<unsigned long long>();
     const bool timed = f->timed;   // (some launch of this frame stored its waves' ticks)
     hipLaunchKernelGGL(k_reduce_counters, dim3(kCounterWords + (timed ? n_groups : 0)), dim3(64), 0, st, ctr, ws.ctr_host,
-                       ws.gtime.as<unsigned>(), paper_waves_per_group(f->W));
+                       ws.gtime.as<unsigned>(), rtamd::paper_waves_per_group(f->W));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ws.ev[3], st));
     HIP_TRY(rtamd::spin_wait(ws.ev[3]));
@@ -965,18 +711,11 @@ int frame_end_body(rt_frame* f, rt_stats* stats) {
     for (int k = 0; k < kCounterWords; ++k) hc[k] = ((volatile unsigned long long*)ws.ctr_host)[k];
     if (timed) {
         // this frame's group costs, by each group's first ext index
-        if (ws.paper_cost.size() >= 64 && !ws.paper_cost.count(f->key)) ws.paper_cost.clear();
-        std::vector<uint32_t>& cost = ws.paper_cost[f->key];
-        cost.resize(f->n_ext, 0);
-        const volatile unsigned int* gc = reinterpret_cast<const volatile unsigned int*>(ws.ctr_host + kCounterWords);
-        for (const auto& c : f->calls) {
-            const std::vector<int32_t>& L = f->stage[c.second];
-            for (size_t g = 0; g < L.size() / 8; ++g) {
-                int32_t e = -1;
-                for (size_t i = 0; i < 8 && e < 0; ++i) e = L[8 * g + i];
-                if (e >= 0) cost[e] = std::max(1u, (unsigned)gc[c.first / 8 + g]);
-            }
-        }
+        const uint64_t key = f->paper.key;
+        if (ws.paper_cost.size() >= 64 && !ws.paper_cost.count(key)) ws.paper_cost.clear();
+        const volatile unsigned int* gcv = reinterpret_cast<const volatile unsigned int*>(ws.ctr_host + kCounterWords);
+        const std::vector<uint32_t> gc(gcv, gcv + n_groups);
+        f->paper_calls.group_costs(gc.data(), ws.paper_cost[key]);
     }
     if (f->bvh_trial >= 0) {
         // the BVH trial frames: their trace kernels' time decides later frames
@@ -989,7 +728,7 @@ int frame_end_body(rt_frame* f, rt_stats* stats) {
     }
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
-        stats->rays_intersect = f->mode == RT_MODE_PAPER ? f->logical_isect : hc[0];
+        stats->rays_intersect = f->mode == RT_MODE_PAPER ? f->paper.logical_isect : hc[0];
         stats->rays_occluded = hc[1];
         stats->rays_traced = hc[0] + hc[1];
         stats->pixels = (uint64_t)f->n_rows * f->W;
@@ -1075,7 +814,9 @@ extern "C" int rt_warmup(int what) {
         // the FP64 render kernels' code object (one per fat binary and
         // device, loaded at its first use; hipFuncGetAttributes loads it)
         hipFuncAttributes a{};
-        HIP_TRY(hipFuncGetAttributes(&a, rtd::std_kernel(false, false, false, true, false, false)));
+        rtamd::KernelVariant lean;   // (k_std_lean<false, 1, false>)
+        lean.wv = 1;
+        HIP_TRY(hipFuncGetAttributes(&a, rtd::std_kernel(lean).fn));
     }
     return RT_OK;
 }
@@ -1099,51 +840,11 @@ hipError_t rtamd::warm_copy_engine(hipStream_t st) {
     return hipMemcpyAsync(host.data(), dev, kBytes, hipMemcpyDeviceToHost, st);
 }
 
-int rtamd::wave_cull_min() {
-    static const int v = [] {
-        const char* e = std::getenv("RT_WV_MIN");
-        return e && *e ? std::max(1, std::atoi(e)) : 4;
-    }();
-    return v;
-}
-
 void rtamd::note_setup_ms(int slot, double ms) {
     if (slot < 4 || slot >= kSetupSlots) return;
     std::lock_guard<std::mutex> lk(g_setup.mu);
     if (slot < kLastBegin || slot == kLastTrace || slot == kSetupCopyEngine) g_setup.extra[slot] += ms;
     else g_setup.extra[slot] = ms;
-}
-
-// Row chunks of a frame or a rank's share (see rt_internal.hpp).
-std::vector<std::pair<int, int>> rtamd::row_chunks(int m, int chunks, int S) {
-    const int64_t units = (m + S - 1) / S;
-    chunks = (int)std::max<int64_t>(1, std::min<int64_t>(chunks, units));
-    const int64_t wsum = (int64_t)chunks * (chunks + 1) / 2;
-    std::vector<std::pair<int, int>> out;
-    int64_t acc = 0;
-    for (int k = 0; k < chunks; ++k) {
-        const int64_t u0 = acc * units / wsum;
-        acc += chunks - k;
-        const int64_t u1 = acc * units / wsum;
-        const int a = (int)std::min<int64_t>(m, u0 * S), b = (int)std::min<int64_t>(m, u1 * S);
-        if (b > a) out.emplace_back(a, b);
-    }
-    if (out.empty()) out.emplace_back(0, 0);
-    return out;
-}
-
-// RT_PAPER_CHUNKS_1GPU (measurement A/B; 1 .. 4, default 1): row chunks of a
-// paper frame rendered by one GPU, alternating between two streams so that
-// chunk k's finish pass overlaps chunk k+1's primary.  Measured on config 5
-// (profiles/r05_ab/ab_paper_chunks_1gpu.txt): 1 chunk 5.34 ms, 2 chunks 5.37,
-// 4 chunks 5.57 - the chunks' own tails and their separate costliest-first
-// orders cost more than the overlapped finish saves - so one launch pair.
-int rtamd::paper_chunks_1gpu() {
-    static const int c = [] {
-        const char* e = std::getenv("RT_PAPER_CHUNKS_1GPU");
-        return e && *e ? std::max(1, std::min(4, std::atoi(e))) : 1;
-    }();
-    return c;
 }
 
 int rtamd::release_device_workspaces(int min_slot) {
@@ -1352,246 +1053,4 @@ extern "C" int rt_framebuffer_to_rgb8_device(const double* fb_dev, size_t n_pixe
     hipLaunchKernelGGL(k_to_rgb8, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, fb_dev, n, rgb8_dev);
     HIP_TRY(hipGetLastError());
     return RT_OK;
-}
-
-// ------------------------------------------------------------- test hooks
-#include "rt_test.h"
-
-extern "C" int rt_test_paper_order(int32_t* list, int n, const uint32_t* cost, int n_cost) {
-    if (n < 0 || n % 16 || (n && !list) || n_cost < 0 || (n_cost && !cost)) return RT_ERR_INVALID_ARG;
-    std::vector<int32_t> L(list, list + n);
-    const std::vector<uint32_t> c(cost, cost + n_cost);
-    order_paper_groups(L, &c);
-    std::copy(L.begin(), L.end(), list);
-    return RT_OK;
-}
-
-extern "C" int rt_test_mt_jump_cpu(int K_blocks, int levels) {
-    // Every radix-R tree polynomial x^(624*K*m*R^j) applied to the seed
-    // window must equal advancing it m*R^j*K twist blocks sequentially.
-    try {
-        std::vector<uint32_t> polys = rtamd::mt_tree_polys(K_blocks, levels);
-        uint32_t base[624];
-        rtamd::mt_first_window(12345u, base);
-        int bad = 0;
-        for (int j = 0; j < levels; ++j) {
-            uint32_t seq[624];
-            std::memcpy(seq, base, sizeof(seq));
-            const uint64_t step = (uint64_t)K_blocks << (rtamd::kMTRadixBits * j);
-            for (int m = 1; m < rtamd::kMTRadix; ++m) {
-                rtamd::mt_advance_blocks_cpu(seq, step);
-                uint32_t jumped[624];
-                rtamd::mt_apply_jump_cpu(polys.data() + ((size_t)j * (rtamd::kMTRadix - 1) + (m - 1)) * 624, base,
-                                         jumped);
-                // bit 31..0 of words 1..623 and the top bit of word 0 define the state
-                bool ok = (jumped[0] & 0x80000000u) == (seq[0] & 0x80000000u);
-                for (int k = 1; k < 624; ++k) ok = ok && jumped[k] == seq[k];
-                if (!ok) ++bad;
-            }
-        }
-        return bad;
-    } catch (...) {
-        return -1;
-    }
-}
-
-extern "C" int rt_test_mt_poly_file(const char* path, int levels) {
-    if (!path || levels <= 0) return RT_ERR_INVALID_ARG;
-    try {
-        std::vector<uint32_t> from_file;
-        if (!rtamd::mt_load_tree_polys(path, rtamd::kTableK, levels, from_file)) return 2;
-        return from_file == rtamd::mt_tree_polys_computed(rtamd::kTableK, levels) ? 0 : 1;
-    } catch (...) {
-        return -1;
-    }
-}
-
-extern "C" int rt_test_jitter_device(int K, int64_t q0, int64_t q1, int64_t first, int64_t count,
-                                     double* out_host) {
-    if (K < 0 || q0 < 0 || q1 <= q0 || (q0 & 1) || (q1 & 1) || !out_host || first * 2 < q0 || (first + count) * 2 > q1)
-        return RT_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RT_ERR_NO_DEVICE;
-    if (K == 0) {   // the frame path: checkpoint table + one-wave fill
-        rtamd::JitterTable T;
-        HIP_TRY(T.ensure((q1 - 1) / ((int64_t)rtamd::kTableK * 624) + 1, nullptr));
-        DBuf dj, ds;
-        const std::vector<rtamd::JRange> ranges{rtamd::JRange{q0, q1, 0}};
-        rtamd::JitterJob job;
-        HIP_TRY(dj.ensure((size_t)(q1 - q0) / 2 * sizeof(double)));
-        HIP_TRY(ds.ensure(rtamd::mt_fill_scratch_bytes(ranges)));
-        HIP_TRY(rtamd::mt_launch_fill(T, ranges, job, ds.p, dj.as<double>(), nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(out_host, dj.as<double>() + (first - q0 / 2), (size_t)count * sizeof(double),
-                          hipMemcpyDeviceToHost));
-        T.release();
-        (void)hipFree(dj.p);
-        (void)hipFree(ds.p);
-        return RT_OK;
-    }
-    rtamd::JitterPlan plan;
-    HIP_TRY(plan.build(K, rtamd::mt_levels_needed(K, q1), nullptr));
-    DBuf dc, dj, ds;
-    const std::vector<rtamd::JRange> ranges{rtamd::JRange{q0, q1, 0}};
-    rtamd::JitterJob job;
-    HIP_TRY(dc.ensure(rtamd::mt_ckpt_words(K, q1) * 4));
-    HIP_TRY(dj.ensure((size_t)(q1 - q0) / 2 * sizeof(double)));
-    HIP_TRY(ds.ensure(rtamd::mt_scratch_bytes(K, ranges)));
-    HIP_TRY(rtamd::mt_launch_jitter(plan, ranges, job, ds.p, dc.as<uint32_t>(), dj.as<double>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out_host, dj.as<double>() + (first - q0 / 2), (size_t)count * sizeof(double),
-                      hipMemcpyDeviceToHost));
-    plan.release();
-    (void)hipFree(dc.p);
-    (void)hipFree(dj.p);
-    (void)hipFree(ds.p);
-    return RT_OK;
-}
-
-extern "C" int rt_test_kernel_name(const rt_scene* s, int mode, int flags, char* out, int cap) {
-    if (!s || !out || cap <= 0) return RT_ERR_INVALID_ARG;
-    try {
-        const rt_scene_desc& d = *rt_scene_get_desc(s);
-        const rtamd::CompiledScene cs = rtamd::compile_scene(d);
-        bool secondary = false;
-        for (int i = 0; i < d.n_materials; ++i)
-            if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) secondary = true;
-        if (d.recursion_limit < 2) secondary = false;
-        const bool eager = cs.has_eager;
-        const bool deep = eager || cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
-        int n_bounded = 0;
-        for (const auto& o : cs.objs)
-            if (o.has_bound && o.kind != rtamd::OBJ_GROUP) ++n_bounded;
-        const bool f32 = (flags & RT_FLAG_FP32) != 0;
-        const bool wv = !(flags & RT_FLAG_NO_CULL) && n_bounded >= rtamd::wave_cull_min();
-        const bool bv = wv && !cs.wchunk.empty() && !(flags & RT_FLAG_NO_BVH);
-        const bool cnt = (flags & RT_FLAG_COUNT_OPS) != 0;
-        const int frames = (secondary && mode == RT_MODE_STANDARD) ? d.recursion_limit - 1 : 0;
-        const bool big = !f32 && (cs.max_ray_depth > kMaxRayStack || cs.max_ivl_depth > kMaxIvlSpill + 2 ||
-                                  frames > kMaxDepth);
-        const char* ns = big ? "rtdb" : f32 ? "rtf" : "rtd";
-        auto tf = [](bool b) { return b ? "true" : "false"; };
-        // (the plain variants: FP64 only, never op-counting)
-        const bool pl = !big && !f32 && !cnt && plain_scene(cs) && [] {
-            const char* e = std::getenv("RT_PLAIN");
-            return !(e && *e == '0');
-        }();
-        std::string name;
-        if (mode == RT_MODE_PAPER) {
-            if (!big && !eager && !deep)
-                name = std::string("k_paper_primary_lean<") + tf(cnt) + ", " + (bv ? "2" : wv ? "1" : "0") + ", false, " +
-                       tf(pl) + ">";
-            else
-                name = std::string("k_paper_primary<") + tf(big || eager) + ", " + tf(big || deep) + ", " + tf(cnt) + ">";
-        } else if (!big && !eager && !deep && !secondary) {
-            name = std::string("k_std_lean<") + tf(cnt) + ", " + (bv ? "2" : wv ? "1" : "0") + ", " + tf(pl) + ">";
-        } else if (!big && !eager && !deep && wv) {   // (secondary here)
-            name = std::string("k_std_secw<") + tf(cnt) + ", " + (bv ? "2" : "1") + ", " + tf(pl) + ">";
-        } else {
-            name = std::string("k_std<") + tf(big || eager) + ", " + tf(big || deep) + ", " + tf(secondary) + ", " +
-                   tf(cnt) + ", false>";
-        }
-        std::snprintf(out, (size_t)cap, "%s::%s", ns, name.c_str());
-        return RT_OK;
-    } catch (const std::exception& e) {
-        rtamd::set_last_error(std::string("scene compile: ") + e.what());
-        return RT_ERR_INVALID_ARG;
-    }
-}
-
-extern "C" int rt_test_kernel_info(const rt_scene* s, int mode, int flags, int32_t* out) {
-    if (!s || !out) return RT_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RT_ERR_NO_DEVICE;
-    try {
-        const rt_scene_desc& d = *rt_scene_get_desc(s);
-        const rtamd::CompiledScene cs = rtamd::compile_scene(d);
-        bool secondary = false;
-        for (int i = 0; i < d.n_materials; ++i)
-            if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) secondary = true;
-        if (d.recursion_limit < 2) secondary = false;
-        const bool deep = cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
-        int n_bounded = 0;
-        for (const auto& o : cs.objs)
-            if (o.has_bound && o.kind != rtamd::OBJ_GROUP) ++n_bounded;
-        const bool wv = !(flags & RT_FLAG_NO_CULL) && n_bounded >= rtamd::wave_cull_min();
-        const bool bv = wv && !cs.has_eager && !deep && !cs.wchunk.empty() && !(flags & RT_FLAG_NO_BVH);
-        const bool f32 = (flags & RT_FLAG_FP32) != 0;
-        const int frames = (secondary && mode == RT_MODE_STANDARD) ? d.recursion_limit - 1 : 0;
-        const bool big = !f32 && (cs.max_ray_depth > kMaxRayStack || cs.max_ivl_depth > kMaxIvlSpill + 2 ||
-                                  frames > kMaxDepth);
-        const bool pl = plain_scene(cs);
-        const void* fn = big ? (mode == RT_MODE_PAPER ? rtdb::paper_kernel(true, true, false, false, false)
-                                                      : rtdb::std_kernel(true, true, secondary, false, false, false))
-                       : mode == RT_MODE_PAPER
-                             ? (f32 ? rtf::paper_kernel(cs.has_eager, deep, wv, bv, pl)
-                                    : rtd::paper_kernel(cs.has_eager, deep, wv, bv, pl))
-                             : (f32 ? rtf::std_kernel(cs.has_eager, deep, secondary, wv, bv, pl)
-                                    : rtd::std_kernel(cs.has_eager, deep, secondary, wv, bv, pl));
-        hipFuncAttributes a{};
-        HIP_TRY(hipFuncGetAttributes(&a, fn));
-        int blocks = 0;
-        const bool paper = mode == RT_MODE_PAPER;
-        const int threads = big ? rtdb::kernel_block_threads(paper)
-                                : f32 ? rtf::kernel_block_threads(paper) : rtd::kernel_block_threads(paper);
-        const size_t pool = big ? rtdb::kernel_pool_bytes(paper)
-                                : f32 ? rtf::kernel_pool_bytes(paper) : rtd::kernel_pool_bytes(paper);
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, pool));
-        out[0] = a.numRegs;                      // VGPRs per lane
-        out[1] = (int32_t)a.localSizeBytes;      // scratch (spill) bytes per lane
-        out[2] = (int32_t)(a.sharedSizeBytes + pool);   // LDS per workgroup (static + the shading pool)
-        out[3] = blocks;                                 // resident workgroups per CU
-        out[4] = blocks * (threads / 64) / 4;            // waves per SIMD (4 SIMDs per CU)
-        out[5] = a.maxThreadsPerBlock;
-        out[6] = wv ? 1 : 0;
-        out[7] = secondary ? 1 : 0;
-        return RT_OK;
-    } catch (const std::exception& e) {
-        rtamd::set_last_error(std::string("scene compile: ") + e.what());
-        return RT_ERR_INVALID_ARG;
-    }
-}
-
-extern "C" int rt_test_wave_bvh(const rt_scene* s, int32_t* counts, int32_t* worig, float* wctab, int cap_objs,
-                                float* wchunk, int cap_chunks) {
-    if (!s || !counts || cap_objs < 0 || cap_chunks < 0) return RT_ERR_INVALID_ARG;
-    try {
-        const rtamd::CompiledScene cs = rtamd::compile_scene(*rt_scene_get_desc(s));
-        const int n = (int)cs.wobjs.size(), nch = (int)(cs.wchunk.size() / 8);
-        counts[0] = n;
-        counts[1] = nch;
-        for (int i = 0; i < std::min(n, cap_objs); ++i) {
-            if (worig) worig[i] = cs.worig[i];
-            if (wctab) std::memcpy(wctab + 8 * (size_t)i, &cs.wctab[8 * (size_t)i], 8 * sizeof(float));
-        }
-        if (wchunk) std::memcpy(wchunk, cs.wchunk.data(), (size_t)std::min(nch, cap_chunks) * 8 * sizeof(float));
-        return RT_OK;
-    } catch (const std::exception& e) {
-        rtamd::set_last_error(std::string("scene compile: ") + e.what());
-        return RT_ERR_INVALID_ARG;
-    }
-}
-
-extern "C" int rt_test_compile_info(const rt_scene* s, int32_t* out) {
-    if (!s || !out) return RT_ERR_INVALID_ARG;
-    try {
-        const rtamd::CompiledScene cs = rtamd::compile_scene(*rt_scene_get_desc(s));
-        int groups = 0, members = 0, ivl_groups = 0, ivl_members = 0;
-        for (const auto& o : cs.objs)
-            if (o.kind == rtamd::OBJ_GROUP) { ++groups; members += o.m; }
-        for (const auto& op : cs.ops)
-            if (op.op == rtamd::OP_IVL_GROUP) { ++ivl_groups; ivl_members += op.top / 2; }
-        out[0] = (int32_t)cs.objs.size();
-        out[1] = groups;
-        out[2] = members;
-        out[3] = (int32_t)cs.ops.size();
-        out[4] = ivl_groups;
-        out[5] = ivl_members;
-        out[6] = cs.has_eager ? 1 : 0;
-        out[7] = cs.max_ivl_depth;
-        return RT_OK;
-    } catch (const std::exception& e) {
-        rtamd::set_last_error(std::string("scene compile: ") + e.what());
-        return RT_ERR_INVALID_ARG;
-    }
 }

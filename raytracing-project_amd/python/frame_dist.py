@@ -6,9 +6,10 @@ cheap sky rows against expensive geometry rows.
 All ranks' row buffers are padded to the same row count so one all_gather
 collects them; rank 0 then scatters the real rows into the frame.
 
-A Python TWIN of the product's partition and chunking (rt_dist.hip
-strip_owners / partition_rows / chunk_bounds; tests/test_host_lib.py pins the
-partitions equal) for CPU tests and tools only: tests/test_dist_gloo.py runs
+A Python TWIN of the product's partition and chunking (csrc/host/frame_plan.cpp
+strip_owners / partition_rows / row_chunks / plan_dist_frame;
+tests/test_host_lib.py pins the partitions equal, tests/test_frame_plan.py the
+chunks and the gather layout) for CPU tests and tools only: tests/test_dist_gloo.py runs
 it over gloo with the CPU oracle as the renderer.  The product's own rank
 protocol (agreements, gathers, placement, failure verdicts) is C++ in
 rt_dist.hip dist_frame; bench.py and the CLI go through it (rt_render_dist,
@@ -25,11 +26,11 @@ def strip_for(mode: int) -> int:
     return PAPER_STRIP if mode == 1 else STRIP
 
 
-ROOT_SHED = {0: 8, 1: 45}   # per mille per rank of the root's weight (rt_dist.hip kRootShedStd / kRootShedPaper)
+ROOT_SHED = {0: 8, 1: 45}   # per mille per rank of the root's weight (frame_plan.hpp kRootShedStd / kRootShedPaper)
 
 
 def strip_owners(n_strips: int, world: int, mode: int = 0, kind: int = 0) -> list[int]:
-    """rt_dist.hip strip_owners: smooth weighted round robin over the strips,
+    """frame_plan.cpp strip_owners: smooth weighted round robin over the strips,
     ties to the rank first in a per-round rotation, the root's weight reduced
     by ROOT_SHED[mode] per mille per rank (FP64 output) for its placement work."""
     if world <= 1:
@@ -85,7 +86,7 @@ def chunk_bounds(m: int, chunks: int, strip: int = 1) -> list[tuple[int, int]]:
     """Split the padded per-rank row list [0, m) into `chunks` contiguous
     pieces of whole strips, of decreasing size (the pipeline units: chunk k is
     gathered while k+1 is traced, so only the smallest, last one's gather is
-    exposed; rt_dist.hip chunk_bounds)."""
+    exposed; frame_plan.cpp row_chunks)."""
     units = (m + strip - 1) // strip if m > 0 else 0
     chunks = max(1, min(chunks, units)) if units > 0 else 1
     wsum = chunks * (chunks + 1) // 2   # decreasing sizes: weights chunks, chunks-1, ..., 1

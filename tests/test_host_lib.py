@@ -223,7 +223,7 @@ def test_paper_code_decoder_matches_reference_expression(rt):
 
 
 def test_paper_launch_order_permutes_whole_blocks(rt):
-    """rt_render.hip order_paper_groups: a paper frame's primary list is
+    """frame_plan.cpp order_paper_groups: a paper frame's primary list is
     relaunched in 16-entry blocks (one workgroup row), costliest first by the
     previous frame's measured 8-entry group costs (keyed by each group's first
     ext index), ties in list order, padding blocks last; any unmeasured group

@@ -1,9 +1,9 @@
-"""Plain-kernel selection (rt_device.hpp CntPlain, rt_render.hip plain_scene):
+"""Plain-kernel selection (rt_device.hpp CntPlain, frame_plan.cpp pick_variant):
 scenes whose objects are all spheres, half-spaces and pokeballs run the lean /
 recursion / paper kernels compiled without transform and CSG code; any
 transform or CSG object keeps the general variants.  The choice is host logic
-(rt_test_kernel_name compiles the scene and names the kernel a frame would
-launch), so this runs without a GPU; the images of both kinds of kernel are
+(rt_test_kernel_name compiles the scene, asks the frame's own pick_variant and
+looks the kernel up in the launch tables), so this runs without a GPU; the images of both kinds of kernel are
 checked against the oracle by the -m gpu parity tests (configs 2, 3, 5 and the
 recursion row on plain kernels, config 4 and the torture scenes on general
 ones)."""

@@ -3,16 +3,20 @@
 //
 // Built by tools/sanitize/Makefile from the SOURCES of librt_host (JSON
 // parser, schema loader, IR, PNG writer), the device-table compiler
-// (scene_compile.cpp) and the C oracle, all with
-// -fsanitize=address,undefined; tests/test_sanitize.py runs it over the
-// example, torture and deep scenes plus malformed JSON.  Per scene: load,
-// compile the device object table, render a band of rows on the oracle in
-// both modes, toByte, PNG.  Exit 0 = no sanitizer report.
+// (scene_compile.cpp), the frame planners (frame_plan.cpp) and the C oracle,
+// all with -fsanitize=address,undefined; tests/test_sanitize.py runs it over
+// the example, torture and deep scenes plus malformed JSON.  Per scene: load,
+// compile the device object table, pick the frame's kernel variant, render a
+// band of rows on the oracle in both modes, toByte, PNG; then the frame
+// planners over the shapes of tests/test_frame_plan.py.  Exit 0 = no
+// sanitizer report.
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
+#include "frame_plan.hpp"
 #include "oracle.h"
 #include "rt.h"
 #include "scene_compile.hpp"
@@ -26,6 +30,11 @@ static int check_file(const char* path, const char* png_out) {
     }
     const rt_scene_desc* d = rt_scene_get_desc(s);
     rtamd::CompiledScene cs = rtamd::compile_scene(*d);
+    for (int mode = 0; mode < 2; ++mode)
+        for (int flags : {0, (int)RT_FLAG_COUNT_OPS, (int)RT_FLAG_NO_CULL, (int)RT_FLAG_NO_BVH, (int)RT_FLAG_FP32}) {
+            rtamd::KernelVariant v;
+            (void)rtamd::pick_variant(cs, *d, mode, flags, true, &v);   // (a refusal is a valid outcome)
+        }
     int W = rt_camera_width(&d->camera), H = rt_camera_height(&d->camera);
     if (W > 64) W = 64;
     if (H > 48) H = 48;
@@ -50,6 +59,57 @@ static int check_file(const char* path, const char* png_out) {
     return 0;
 }
 
+// The frame planners at the shapes tests/test_frame_plan.py asserts on (here
+// only for the sanitizers' sake: every index they compute is exercised).
+static size_t check_plans() {
+    size_t sum = 0;
+    const int dist[][4] = {{2160, 8, 0, 4}, {4320, 8, 1, 2}, {2160, 3, 0, 4}, {4320, 3, 1, 2}, {17, 4, 0, 4},
+                           {17, 4, 1, 2},   {5, 8, 0, 4},    {5, 8, 1, 2},    {1, 1, 0, 4},    {1, 1, 1, 2}};
+    for (const auto& c : dist)
+        for (int kind = 0; kind < 2; ++kind)
+            for (int rank = 0; rank < c[1]; ++rank) {
+                const rtamd::DistPlan p = rtamd::plan_dist_frame(c[0], c[1], rank, c[2], kind ? 0 : rtamd::root_shed(c[2]),
+                                                                 c[3], rank == 0);
+                sum += p.rows.size() + p.bounds.size() + p.rowtab.size();
+            }
+    const std::vector<std::vector<int32_t>> std_rows = {{4, 3, 2, 1, 0}, {0, 2, 4}, {2, 0, 1}};
+    for (const auto& rows : std_rows) sum += rtamd::plan_std_frame(3, 5, rows.data(), (int)rows.size(), 64 * 624).jranges.size();
+    struct PaperCase {
+        int W, H;
+        std::vector<int32_t> rows;
+        std::vector<std::pair<int, int>> calls;
+    };
+    auto iota = [](int a, int b) {
+        std::vector<int32_t> v;
+        for (int i = a; i < b; ++i) v.push_back(i);
+        return v;
+    };
+    std::vector<int32_t> split = iota(0, 30), tail = iota(60, 70);
+    split.insert(split.end(), tail.begin(), tail.end());
+    const std::vector<PaperCase> paper = {{17, 1, iota(0, 1), {{0, 1}}},       {17, 2, iota(0, 2), {{0, 2}}},
+                                          {17, 31, iota(0, 31), {{0, 30}, {30, 31}}}, {1, 70, split, {{0, 40}}},
+                                          {5, 70, iota(0, 60), {{0, 30}, {30, 60}}}};
+    for (const PaperCase& pc : paper) {
+        const rtamd::PaperPlan p = rtamd::plan_paper_frame(7, pc.W, pc.H, RT_MODE_PAPER, 0, pc.rows.data(), (int)pc.rows.size());
+        rtamd::PaperCalls calls;
+        calls.reset(&p);
+        std::vector<uint32_t> gc;
+        for (size_t k = 0; k < pc.calls.size(); ++k) {
+            const rtamd::PaperCalls::Call c = calls.next_call(pc.calls[k].first, pc.calls[k].second, k + 1);
+            sum += c.list->size() + c.wait.size();
+        }
+        gc.assign((size_t)calls.list_used() / 8, 3);
+        std::vector<uint32_t> cost;
+        calls.group_costs(gc.data(), cost);
+        calls.rollback();
+        // the same frame again, costliest blocks first
+        calls.reset(&p);
+        for (size_t k = 0; k < pc.calls.size(); ++k) sum += calls.next_call(pc.calls[k].first, pc.calls[k].second, 1, &cost).list->size();
+        sum += p.aux_ints() + p.gtime_words() + (size_t)p.logical_isect;
+    }
+    return sum;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: host_check <out.png> <scene.json>...\n");
@@ -64,5 +124,6 @@ int main(int argc, char** argv) {
         rt_scene* s = nullptr;
         if (rt_scene_load_json_text(t, std::strlen(t), &s) == RT_OK) rt_scene_destroy(s);
     }
+    std::printf("plans %zu\n", check_plans());
     return bad ? 1 : 0;
 }

@@ -1,5 +1,5 @@
 """Per-strip trace cost of a BASELINE config on one GPU, and what it implies
-for the multi-GPU row partition (rt_dist.hip strip_owners / partition_rows).
+for the multi-GPU row partition (frame_plan.cpp strip_owners / partition_rows).
 
 Each strip of `--strip` rows (default: the product's for the mode) is traced
 alone through rt_render_rows_device, `--reps` times, min kernel ms kept (a
