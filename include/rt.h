@@ -23,6 +23,10 @@
  *                               be gathered while later chunks are traced
  *   rt_scatter_rows_device   <- (no reference equivalent: places gathered row
  *                               bands into the full framebuffer on rank 0)
+ *   rt_query_intersect       <- Scene::intersect, a batch of rays
+ *                               raytracer/src/scene.cpp:10-24
+ *   rt_query_occluded        <- Scene::occluded, a batch of rays
+ *                               raytracer/src/scene.cpp:33-42
  *   rt_framebuffer_to_rgb8   <- framebuffer_to_mat_bgr8 / toByte
  *                               raytracer/src/main.cpp:19-34, core.h:313-316
  *   rt_write_png             <- cv::imwrite (main.cpp:86-89)
@@ -54,7 +58,10 @@ extern "C" {
                               5: rt_dist_set_timeout, per-frame rank agreement,
                                  rt_host_register / rt_host_unregister
                               6: rt_dist_frame_split, rt_warmup; the frame descriptor
-                                 carries the scene hash and the root strip shed */
+                                 carries the scene hash and the root strip shed
+                              (still 6: the batched ray queries rt_query_intersect /
+                               rt_query_occluded and their *_device forms, rt_ray and
+                               rt_hit, are pure additions) */
 
 /* ---------------------------------------------------------------- errors */
 enum rt_status {
@@ -364,6 +371,55 @@ int rt_scatter_rows_device(const double* src_dev, const int32_t* rows_dev, int n
 /* Device-side toByte + RGB packing: rgb8_dev[W*H*3]. */
 int rt_framebuffer_to_rgb8_device(const double* fb_dev, size_t n_pixels,
                                   uint8_t* rgb8_dev, void* hip_stream);
+
+/* ------------------------------------------------------- ray queries
+ * Scene::intersect (closest hit, scene.cpp:10-24) and Scene::occluded (any
+ * hit in a segment, scene.cpp:33-42) for a batch of caller-given rays: the
+ * reference's two other public seams on its hot path (picking, visibility
+ * probes, collision, light baking), on the device.
+ *
+ * A ray is the reference's Ray(o, d): d is normalised as in core.h:278 (a
+ * direction of length <= 1e-6 becomes (0, 1, 0)), and t, tmin, tmax are in
+ * world units along the normalised direction; tmax may be +inf.  The closest
+ * hit applies each object's own accept rule with the tightening tmax, so ties
+ * resolve exactly as in the reference; occluded is "any object's intersect in
+ * [tmin, tmax]".  FP64, the parity path; the scene's camera plays no part. */
+typedef struct rt_ray {        /* 64 B */
+    double o[3];
+    double d[3];
+    double tmin, tmax;
+} rt_ray;
+typedef struct rt_hit {        /* 64 B; geometry.h:25-46 Hit */
+    double t;
+    double p[3];
+    double n[3];
+    int32_t mat;               /* material index; -1 on a miss (every other field 0) */
+    int32_t front_face;
+} rt_hit;
+/* hits_host[i] = Scene::intersect(rays_host[i]) for i < n; hit_mask_host (may
+ * be NULL) receives 1 for a hit and 0 for a miss.  Rays and results cross to
+ * the device and back in chunks of bounded size.  flags: RT_FLAG_NONE or
+ * RT_FLAG_NO_CULL (identical results; RT_FLAG_NO_BVH / RT_FLAG_FORCE_BVH
+ * have no effect: queries walk the flat object list, whose results equal the
+ * wave BVH's); RT_FLAG_FP32 and RT_FLAG_COUNT_OPS are RT_ERR_UNSUPPORTED, as
+ * is a scene beyond the device stacks.  n == 0 is RT_OK without a launch.
+ * stats (may be NULL): rays_intersect = rays_traced = n, ms_kernel, ms_total.
+ * Uses the current HIP device and shares its resident scene copy with the
+ * frames (a query after a frame of the same scene uploads nothing, nor a
+ * frame after a query); waits for an open frame of the device; blocks until
+ * done. */
+int rt_query_intersect(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, rt_hit* hits_host,
+                       uint8_t* hit_mask_host, rt_stats* stats);
+/* occluded_host[i] = Scene::occluded(rays_host[i]) as 1 / 0;
+ * stats->rays_occluded = rays_traced = n. */
+int rt_query_occluded(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, uint8_t* occluded_host,
+                      rt_stats* stats);
+/* The same with rays and results already on the device, enqueued on
+ * hip_stream (NULL = the default stream); blocks until done. */
+int rt_query_intersect_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, rt_hit* hits_dev,
+                              uint8_t* hit_mask_dev, void* hip_stream, rt_stats* stats);
+int rt_query_occluded_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, uint8_t* occluded_dev,
+                             void* hip_stream, rt_stats* stats);
 
 /* ------------------------------------------------------------ host I/O */
 /* toByte(v) = round(clamp01(v)*255) (core.h:316), RGB order. */

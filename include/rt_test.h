@@ -55,6 +55,13 @@ int rt_test_kernel_info(const struct rt_scene* s, int mode, int flags, int32_t* 
  * frame refuses (RT_ERR_UNSUPPORTED) is refused here too.  Host only. */
 int rt_test_kernel_name(const struct rt_scene* s, int mode, int flags, char* out, int cap);
 
+/* The same for a ray query (rt_query_intersect / rt_query_occluded): kind 0 the
+ * closest-hit kernel, 1 the any-hit one (e.g. "rtd::k_query_isect<false, false,
+ * true>"): the query's own kernel choice (frame_plan.hpp pick_query_variant)
+ * looked up in the query table, so the flags and scenes a query refuses are
+ * refused here too.  Host only. */
+int rt_test_query_kernel_name(const struct rt_scene* s, int kind, int flags, char* out, int cap);
+
 /* GPU: the shared-denominator division of the device code (rt_device.hpp
  * div3) next to the compiler's own division on the same inputs:
  * div3_host[3i+k] and plain_host[3i+k] = a[3i+k] / b[i].  Tests require the

@@ -13,6 +13,8 @@
 //   k_paper_finish: edge strength from the stored neighbour hits + hatch.
 // The framebuffer, jitter draws and paper hit records stay double in both
 // precisions (the float kernels convert on load / store).
+// (The batched ray-query kernels k_query_isect / k_query_occl and their table
+// live in rt_query_kernels.hpp, built in translation units of their own.)
 
 namespace RT_NS {
 
@@ -554,44 +556,6 @@ __global__ __launch_bounds__(64 * kFinishRows) void k_paper_finish(PaperParams P
         if (ri >= P.n_rows) return;
         paper_finish_px<CODES, PAIR>(P, x, ri);
     }
-}
-
-// bv: the wave BVH kernels, whose object list is the Morton-ordered one
-DevScene make_scene(const SceneView& V, bool bv = false) {
-    DevScene S;
-    S.nodes = static_cast<const NodeT*>(V.nodes);
-    S.mats = static_cast<const MatT*>(V.mats);
-    S.lights = static_cast<const LightT*>(V.lights);
-    S.dlights = static_cast<const DLightT*>(V.dlights);
-    S.objs = bv ? V.wobjs : V.objs;
-    S.ops = V.ops;
-    S.gb = V.gb;
-    S.ctab = reinterpret_cast<const float4*>(bv ? V.wctab : V.ctab);
-    S.lrec = reinterpret_cast<const float4*>(bv ? V.lwrec : V.lrec);
-    S.lgb = reinterpret_cast<const float4*>(V.lgb);
-    S.n_gb = V.n_gb;
-    S.fold = static_cast<const FoldT*>(V.fold);
-    S.worig = bv ? V.worig : nullptr;
-    S.wchunk = reinterpret_cast<const float4*>(bv ? V.wchunk : nullptr);
-    S.n_chunks = bv ? V.n_chunks : 0;
-    S.n_lights = V.n_lights;
-    S.n_dlights = V.n_dlights;
-    S.n_bounded = V.n_bounded;
-    S.n_lead = bv ? 0 : V.n_lead;
-    S.n_objs = bv ? V.n_wobjs : V.n_objs;
-    S.cam_nx = V.cam_nx;
-    S.cam_ny = V.cam_ny;
-    S.rec_limit = V.rec_limit;
-    S.cull = V.cull;
-    for (int i = 0; i < 3; ++i) {
-        S.eye[i] = (real)V.eye[i];
-        S.P[i] = (real)V.P[i];
-    }
-    S.Lx = (real)V.Lx;
-    S.Ly = (real)V.Ly;
-    S.medium_index = (real)V.medium_index;
-    S.bg_mat = V.bg_mat;
-    return S;
 }
 
 // Dynamic LDS of the kernels that shade (lds_pool): one region per wave

@@ -7,3 +7,12 @@
 #define RT_NO_PLAIN   // (no plain kernel variants in the FP32 diagnostic build)
 #include "rt_device.hpp"
 #include "rt_kernels.hpp"
+
+// (no FP32 ray queries: rt_query_kernels.hpp is built for rtd and rtdb only)
+namespace rtf {
+hipError_t launch_query(const rtamd::KernelVariant&, int, hipStream_t, const rtamd::SceneView&,
+                        const rtamd::QueryParams&) {
+    return hipErrorInvalidDeviceFunction;
+}
+rtamd::KernelEntry query_kernel(const rtamd::KernelVariant&, int) { return rtamd::KernelEntry{nullptr, nullptr}; }
+}  // namespace rtf

@@ -123,6 +123,17 @@ struct PaperParams {
     unsigned long long* counters;
 };
 
+// A batch of ray queries (rt_query_intersect / rt_query_occluded): ray i of
+// rays[0, n) is lane i % 64 of wave i / 64.  Closest hit: hits[i] and, when
+// mask is set, mask[i] = 1 / 0; any hit: mask[i] = 1 / 0 (hits unused).
+struct QueryParams {
+    const rt_ray* rays;
+    size_t n;
+    rt_hit* hits;
+    uint8_t* mask;
+};
+enum { kQueryIsect = 0, kQueryOccl = 1 };   // query kinds (k_query_isect / k_query_occl)
+
 // Paper mode's output alphabet (tracer.cpp:258-281): every pixel is grey
 // (r = g = b) and a function of the edge strength - the max of the constants
 // {0.9, 0.6, 0.5, 0.3} over the neighbour tests, or 0, halved when a
@@ -160,7 +171,9 @@ struct KernelEntry {
 
 // The trace kernels of one namespace (rt_kernels.hpp), by KernelVariant
 // (frame_plan.hpp).  launch_*: hipErrorInvalidDeviceFunction when the
-// namespace has no kernel for the variant.
+// namespace has no kernel for the variant.  launch_query / query_kernel: the
+// ray-query kernels (rt_query_kernels.hpp, their own translation units; rtf
+// has none).
 #define RT_DECLARE_LAUNCHERS(NS)                                                                                  \
     namespace NS {                                                                                                \
     hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,               \
@@ -172,6 +185,9 @@ struct KernelEntry {
     rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v);                                               \
     int kernel_block_threads(bool paper);                                                                         \
     size_t kernel_pool_bytes(bool paper);                                                                         \
+    hipError_t launch_query(const rtamd::KernelVariant& v, int kind, hipStream_t st, const rtamd::SceneView& V,   \
+                            const rtamd::QueryParams& P);                                                         \
+    rtamd::KernelEntry query_kernel(const rtamd::KernelVariant& v, int kind);                                     \
     }
 RT_DECLARE_LAUNCHERS(rtd)
 RT_DECLARE_LAUNCHERS(rtf)
@@ -199,6 +215,16 @@ inline KernelEntry trace_kernel(const KernelVariant& v, bool paper) {
     if (v.ns == KernelVariant::kRtf) return paper ? rtf::paper_kernel(v) : rtf::std_kernel(v);
     if (v.ns == KernelVariant::kRtdb) return paper ? rtdb::paper_kernel(v) : rtdb::std_kernel(v);
     return paper ? rtd::paper_kernel(v) : rtd::std_kernel(v);
+}
+inline hipError_t launch_query(const KernelVariant& v, int kind, hipStream_t st, const SceneView& V,
+                               const QueryParams& P) {
+    return v.ns == KernelVariant::kRtf ? rtf::launch_query(v, kind, st, V, P)
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_query(v, kind, st, V, P)
+                                                                      : rtd::launch_query(v, kind, st, V, P);
+}
+inline KernelEntry query_kernel(const KernelVariant& v, int kind) {
+    return v.ns == KernelVariant::kRtf ? rtf::query_kernel(v, kind)
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::query_kernel(v, kind) : rtd::query_kernel(v, kind);
 }
 inline int trace_block_threads(const KernelVariant& v, bool paper) {
     return v.ns == KernelVariant::kRtf ? rtf::kernel_block_threads(paper)

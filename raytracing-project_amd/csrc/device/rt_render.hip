@@ -13,6 +13,9 @@
 // (csrc/host/frame_plan.hpp: pick_variant, plan_std_frame, plan_paper_frame,
 // PaperCalls); rt_frame_begin / trace / end here execute that plan.  The
 // rt_test_* hooks live in rt_test_hooks.hip.
+// Ray queries (rt_query_intersect / rt_query_occluded, Scene::intersect /
+// Scene::occluded for caller-given rays, scene.cpp:10-42): query_impl here,
+// on the frames' workspace and resident scene; kernels in rt_query_kernels.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -40,6 +43,7 @@
 using rtamd::kCounterSlots;
 using rtamd::kCounterWords;
 using rtamd::PaperParams;
+using rtamd::QueryParams;
 using rtamd::SceneView;
 using rtamd::StdParams;
 
@@ -149,6 +153,7 @@ struct Workspace {
     DBuf nodes_f, mats_f, lights_f, dlights_f, fold_f;   // float copies (RT_FLAG_FP32)
     DBuf rows, jit, ckpt, jscratch, counters;
     DBuf paper_i, paper_d, paper_aux, fb;
+    DBuf q_rays, q_hits, q_mask;              // ray queries from host memory: one chunk's rays / hits / flags
     rtamd::JitterTable jtab;                  // mt19937(12345) checkpoint table (resident)
     rtamd::JitterJob jjob;
     rtamd::PinnedArena up;                    // page-locked staging of a frame's uploads (pinned.hpp)
@@ -289,6 +294,127 @@ void make_float_scene(SceneCache& f) {
     }
 }
 
+// The scene resident in the workspace: compiled and uploaded once (on st), and
+// found there by every later frame or ray query of it on the device.  The
+// caller holds the workspace lock and has reset the staging arena.
+int scene_resident(Workspace& ws, const rt_scene* s, const rt_scene_desc& d, bool fp32, hipStream_t st) {
+    SceneCache& sc = ws.sc;
+    if (sc.valid && sc.uid == rtamd::scene_uid(s) && sc.fp32 == fp32) return RT_OK;
+    // compile + upload the scene once; later frames of it find it resident
+    // (uploads from the page-locked arena: plain DMA, no pageable staging)
+    const auto t_sc = SClock::now();
+    struct AddTime {
+        SClock::time_point t;
+        ~AddTime() {
+            std::lock_guard<std::mutex> lk(g_setup.mu);
+            g_setup.scene_ms += ms_since(t);
+        }
+    } add_scene_time{t_sc};
+    sc.valid = false;
+    try {
+        sc.cs = rtamd::compile_scene(d);
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("scene compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+    sc.nodes.assign(d.nodes, d.nodes + d.n_nodes);
+    for (rt_node& n : sc.nodes)   // pick_region's acos thresholds (device copy only)
+        if (n.kind == RT_NODE_POKEBALL) rtamd::pokeball_thresholds(n.v[5], n.v[6], n.v[rtamd::kPokeXb], n.v[rtamd::kPokeXi]);
+    sc.mats.assign(d.materials, d.materials + d.n_materials);
+    // device material table: K_a premultiplied by the scene's I_a (the
+    // reference's E_a = mul(m.ambient, scene.ambient), one double product
+    // per channel, shading.cpp:39), and one extra slot whose albedo is the
+    // background colour (DevScene::bg_mat)
+    for (rt_material& m : sc.mats)
+        for (int c = 0; c < 3; ++c) m.ambient[c] = m.ambient[c] * d.ambient[c];
+    {
+        rt_material bgm{};
+        for (int c = 0; c < 3; ++c) bgm.albedo[c] = d.background[c];
+        sc.mats.push_back(bgm);
+    }
+    sc.lights.assign(d.lights, d.lights + d.n_lights);
+    sc.dlights.assign(d.dir_lights, d.dir_lights + d.n_dir_lights);
+    if (fp32) {
+        make_float_scene(sc);
+        HIP_TRY(upload(ws.nodes_f, sc.nodes_f, st, &ws.up));
+        HIP_TRY(upload(ws.mats_f, sc.mats_f, st, &ws.up));
+        HIP_TRY(upload(ws.lights_f, sc.lights_f, st, &ws.up));
+        HIP_TRY(upload(ws.dlights_f, sc.dlights_f, st, &ws.up));
+        HIP_TRY(upload(ws.fold_f, sc.fold_f, st, &ws.up));
+    } else {
+        HIP_TRY(upload(ws.nodes, sc.nodes, st, &ws.up));
+        HIP_TRY(upload(ws.mats, sc.mats, st, &ws.up));
+        HIP_TRY(upload(ws.lights, sc.lights, st, &ws.up));
+        HIP_TRY(upload(ws.dlights, sc.dlights, st, &ws.up));
+        HIP_TRY(upload(ws.fold, sc.cs.fold, st, &ws.up));
+    }
+    HIP_TRY(upload(ws.objs, sc.cs.objs, st, &ws.up));
+    HIP_TRY(upload(ws.ops, sc.cs.ops, st, &ws.up));
+    HIP_TRY(upload(ws.gb, sc.cs.gbounds, st, &ws.up));
+    HIP_TRY(upload(ws.ctab, sc.cs.ctab, st, &ws.up));
+    HIP_TRY(upload(ws.lrec, sc.cs.lrec, st, &ws.up));
+    HIP_TRY(upload(ws.lwrec, sc.cs.lwrec, st, &ws.up));
+    HIP_TRY(upload(ws.lgb, sc.cs.lgb, st, &ws.up));
+    HIP_TRY(upload(ws.wobjs, sc.cs.wobjs, st, &ws.up));
+    HIP_TRY(upload(ws.wctab, sc.cs.wctab, st, &ws.up));
+    HIP_TRY(upload(ws.worig, sc.cs.worig, st, &ws.up));
+    HIP_TRY(upload(ws.wchunk, sc.cs.wchunk, st, &ws.up));
+    sc.uid = rtamd::scene_uid(s);
+    sc.fp32 = fp32;
+    sc.valid = true;
+    sc.bvh_trial = 0;   // (a new scene: its own BVH trial)
+    sc.bvh_key = 0;
+    return RT_OK;
+}
+
+// The launch interface's view of the resident scene (scene_resident) for
+// (flags, precision); n_chunks: the wave BVH unless RT_FLAG_NO_BVH (a frame's
+// BVH trial may still run without it).
+void scene_view(const Workspace& ws, const rt_scene_desc& d, int flags, bool fp32, SceneView& S) {
+    const rtamd::CompiledScene& cs = ws.sc.cs;
+    S.nodes = fp32 ? ws.nodes_f.p : ws.nodes.p;
+    S.mats = fp32 ? ws.mats_f.p : ws.mats.p;
+    S.lights = fp32 ? ws.lights_f.p : ws.lights.p;
+    S.dlights = fp32 ? ws.dlights_f.p : ws.dlights.p;
+    S.fold = fp32 ? ws.fold_f.p : ws.fold.p;
+    S.n_dlights = d.n_dir_lights;
+    S.objs = ws.objs.as<rtamd::DevObj>();
+    S.ops = ws.ops.as<rtamd::DevOp>();
+    S.gb = ws.gb.as<float>();
+    S.ctab = ws.ctab.as<float>();
+    S.lrec = ws.lrec.as<float>();
+    S.lwrec = ws.lwrec.as<float>();
+    S.lgb = ws.lgb.as<float>();
+    S.n_gb = (int)(cs.gbounds.size() / 4);
+    S.wobjs = ws.wobjs.as<rtamd::DevObj>();
+    S.wctab = ws.wctab.as<float>();
+    S.worig = ws.worig.as<int32_t>();
+    S.wchunk = ws.wchunk.as<float>();
+    S.n_wobjs = (int)cs.wobjs.size();
+    S.n_chunks = (flags & RT_FLAG_NO_BVH) ? 0 : (int)(cs.wchunk.size() / 8);
+    S.n_lights = d.n_lights;
+    S.n_objs = (int)cs.objs.size();
+    S.n_bounded = 0;
+    for (const auto& o : cs.objs)
+        if (o.has_bound && o.kind != rtamd::OBJ_GROUP) ++S.n_bounded;
+    S.cam_nx = rt_camera_width(&d.camera);
+    S.cam_ny = rt_camera_height(&d.camera);
+    S.rec_limit = d.recursion_limit;
+    S.cull = (flags & RT_FLAG_NO_CULL) ? 0 : 1;
+    {
+        static const bool lead_on = [] { const char* e = std::getenv("RT_LEAD"); return !(e && *e == '0'); }();
+        S.n_lead = lead_on ? cs.n_lead : 0;   // (RT_LEAD=0: measurement A/B)
+    }
+    for (int i = 0; i < 3; ++i) {
+        S.eye[i] = d.camera.eye[i];
+        S.P[i] = d.camera.P[i];
+    }
+    S.Lx = d.camera.Lx;
+    S.Ly = d.camera.Ly;
+    S.medium_index = d.medium_index;
+    S.bg_mat = d.n_materials;
+}
+
 int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int32_t* rows_host, int n_rows,
                 hipStream_t st, rt_frame** out) {
     const auto t_start = std::chrono::steady_clock::now();
@@ -330,71 +456,9 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
     const bool fp32 = (flags & RT_FLAG_FP32) != 0;
     SceneCache& sc = ws.sc;
     ws.up.reset();   // (the previous frame's uploads completed: its rt_frame_end synchronised)
-    if (!sc.valid || sc.uid != rtamd::scene_uid(s) || sc.fp32 != fp32) {
-        // compile + upload the scene once; later frames of it find it resident
-        // (uploads from the page-locked arena: plain DMA, no pageable staging)
-        const auto t_sc = SClock::now();
-        struct AddTime {
-            SClock::time_point t;
-            ~AddTime() {
-                std::lock_guard<std::mutex> lk(g_setup.mu);
-                g_setup.scene_ms += ms_since(t);
-            }
-        } add_scene_time{t_sc};
-        sc.valid = false;
-        try {
-            sc.cs = rtamd::compile_scene(d);
-        } catch (const std::exception& e) {
-            rtamd::set_last_error(std::string("scene compile: ") + e.what());
-            return RT_ERR_INVALID_ARG;
-        }
-        sc.nodes.assign(d.nodes, d.nodes + d.n_nodes);
-        for (rt_node& n : sc.nodes)   // pick_region's acos thresholds (device copy only)
-            if (n.kind == RT_NODE_POKEBALL) rtamd::pokeball_thresholds(n.v[5], n.v[6], n.v[rtamd::kPokeXb], n.v[rtamd::kPokeXi]);
-        sc.mats.assign(d.materials, d.materials + d.n_materials);
-        // device material table: K_a premultiplied by the scene's I_a (the
-        // reference's E_a = mul(m.ambient, scene.ambient), one double product
-        // per channel, shading.cpp:39), and one extra slot whose albedo is the
-        // background colour (DevScene::bg_mat)
-        for (rt_material& m : sc.mats)
-            for (int c = 0; c < 3; ++c) m.ambient[c] = m.ambient[c] * d.ambient[c];
-        {
-            rt_material bgm{};
-            for (int c = 0; c < 3; ++c) bgm.albedo[c] = d.background[c];
-            sc.mats.push_back(bgm);
-        }
-        sc.lights.assign(d.lights, d.lights + d.n_lights);
-        sc.dlights.assign(d.dir_lights, d.dir_lights + d.n_dir_lights);
-        if (fp32) {
-            make_float_scene(sc);
-            HIP_TRY(upload(ws.nodes_f, sc.nodes_f, st, &ws.up));
-            HIP_TRY(upload(ws.mats_f, sc.mats_f, st, &ws.up));
-            HIP_TRY(upload(ws.lights_f, sc.lights_f, st, &ws.up));
-            HIP_TRY(upload(ws.dlights_f, sc.dlights_f, st, &ws.up));
-            HIP_TRY(upload(ws.fold_f, sc.fold_f, st, &ws.up));
-        } else {
-            HIP_TRY(upload(ws.nodes, sc.nodes, st, &ws.up));
-            HIP_TRY(upload(ws.mats, sc.mats, st, &ws.up));
-            HIP_TRY(upload(ws.lights, sc.lights, st, &ws.up));
-            HIP_TRY(upload(ws.dlights, sc.dlights, st, &ws.up));
-            HIP_TRY(upload(ws.fold, sc.cs.fold, st, &ws.up));
-        }
-        HIP_TRY(upload(ws.objs, sc.cs.objs, st, &ws.up));
-        HIP_TRY(upload(ws.ops, sc.cs.ops, st, &ws.up));
-        HIP_TRY(upload(ws.gb, sc.cs.gbounds, st, &ws.up));
-        HIP_TRY(upload(ws.ctab, sc.cs.ctab, st, &ws.up));
-        HIP_TRY(upload(ws.lrec, sc.cs.lrec, st, &ws.up));
-        HIP_TRY(upload(ws.lwrec, sc.cs.lwrec, st, &ws.up));
-        HIP_TRY(upload(ws.lgb, sc.cs.lgb, st, &ws.up));
-        HIP_TRY(upload(ws.wobjs, sc.cs.wobjs, st, &ws.up));
-        HIP_TRY(upload(ws.wctab, sc.cs.wctab, st, &ws.up));
-        HIP_TRY(upload(ws.worig, sc.cs.worig, st, &ws.up));
-        HIP_TRY(upload(ws.wchunk, sc.cs.wchunk, st, &ws.up));
-        sc.uid = rtamd::scene_uid(s);
-        sc.fp32 = fp32;
-        sc.valid = true;
-        sc.bvh_trial = 0;   // (a new scene: its own BVH trial)
-        sc.bvh_key = 0;
+    {
+        const int rv = scene_resident(ws, s, d, fp32, st);
+        if (rv != RT_OK) return rv;
     }
     const rtamd::CompiledScene& cs = sc.cs;
     f->st = st;
@@ -417,26 +481,7 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
     }
 
     SceneView& S = f->S;
-    S.nodes = fp32 ? ws.nodes_f.p : ws.nodes.p;
-    S.mats = fp32 ? ws.mats_f.p : ws.mats.p;
-    S.lights = fp32 ? ws.lights_f.p : ws.lights.p;
-    S.dlights = fp32 ? ws.dlights_f.p : ws.dlights.p;
-    S.fold = fp32 ? ws.fold_f.p : ws.fold.p;
-    S.n_dlights = d.n_dir_lights;
-    S.objs = ws.objs.as<rtamd::DevObj>();
-    S.ops = ws.ops.as<rtamd::DevOp>();
-    S.gb = ws.gb.as<float>();
-    S.ctab = ws.ctab.as<float>();
-    S.lrec = ws.lrec.as<float>();
-    S.lwrec = ws.lwrec.as<float>();
-    S.lgb = ws.lgb.as<float>();
-    S.n_gb = (int)(sc.cs.gbounds.size() / 4);
-    S.wobjs = ws.wobjs.as<rtamd::DevObj>();
-    S.wctab = ws.wctab.as<float>();
-    S.worig = ws.worig.as<int32_t>();
-    S.wchunk = ws.wchunk.as<float>();
-    S.n_wobjs = (int)cs.wobjs.size();
-    S.n_chunks = (flags & RT_FLAG_NO_BVH) ? 0 : (int)(cs.wchunk.size() / 8);
+    scene_view(ws, d, flags, fp32, S);
     f->bvh_trial = -1;
     if (S.n_chunks > 0 && !(flags & (RT_FLAG_NO_CULL | RT_FLAG_FORCE_BVH)) && bvh_ab()) {
         const uint64_t key = ((uint64_t)(uint32_t)W << 40) ^ ((uint64_t)(uint32_t)H << 20) ^ ((uint64_t)n_rows << 2) ^
@@ -448,33 +493,12 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
         if (sc.bvh_trial < 2) f->bvh_trial = sc.bvh_trial;
         if (sc.bvh_trial == 1 || (sc.bvh_trial == 2 && sc.bvh_off)) S.n_chunks = 0;
     }
-    S.n_lights = d.n_lights;
-    S.n_objs = (int)cs.objs.size();
-    S.n_bounded = 0;
-    for (const auto& o : cs.objs)
-        if (o.has_bound && o.kind != rtamd::OBJ_GROUP) ++S.n_bounded;
-    S.cam_nx = rt_camera_width(&d.camera);
-    S.cam_ny = rt_camera_height(&d.camera);
-    S.rec_limit = d.recursion_limit;
-    S.cull = (flags & RT_FLAG_NO_CULL) ? 0 : 1;
-    {
-        static const bool lead_on = [] { const char* e = std::getenv("RT_LEAD"); return !(e && *e == '0'); }();
-        S.n_lead = lead_on ? cs.n_lead : 0;   // (RT_LEAD=0: measurement A/B)
-    }
     // the trace kernel (the stack tiers, the culling and plain variants);
     // this frame's BVH trial may run it without the wave BVH
     {
         const int rv = rtamd::pick_variant(cs, d, mode, flags, S.n_chunks > 0, &f->kv);
         if (rv != RT_OK) return rv;
     }
-    for (int i = 0; i < 3; ++i) {
-        S.eye[i] = d.camera.eye[i];
-        S.P[i] = d.camera.P[i];
-    }
-    S.Lx = d.camera.Lx;
-    S.Ly = d.camera.Ly;
-    S.medium_index = d.medium_index;
-    S.bg_mat = d.n_materials;
 
     if (n_rows > 0 && mode == RT_MODE_STANDARD) {
         f->std_plan = rtamd::plan_std_frame(W, H, rows_host, n_rows, (int64_t)rtamd::kTableK * 624);
@@ -766,6 +790,112 @@ int render_rows_impl(const rt_scene* s, int W, int H, int mode, int flags, const
     return rc != RT_OK ? rc : rc2;
 }
 
+// ------------------------------------------------------------- ray queries
+// Rays of one launch: 2^30 (the grid's x extent holds 2^31 - 1 one-wave
+// workgroups); rays of one chunk of a query from host memory: 2^20, i.e.
+// 64 MiB of rays + 64 MiB of hits + 1 MiB of flags in the workspace, large
+// enough that a chunk's launch and copy overheads vanish in its transfers.
+constexpr size_t kQueryLaunchRays = (size_t)1 << 30;
+constexpr size_t kQueryChunkRays = (size_t)1 << 20;
+
+// rt_query_{intersect,occluded}[_device]: kind rtamd::kQueryIsect / kQueryOccl.
+// host: rays / hits / mask are host memory, moved through the workspace's
+// chunk buffers; else device memory, traced in place on st.  Holds the
+// workspace lock like a frame, and returns with st drained.
+int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays, size_t n, int flags, rt_hit* hits,
+               uint8_t* mask, bool host, hipStream_t st, rt_stats* stats) {
+    const auto t_start = SClock::now();
+    const auto fail = [what](const char* msg, int rc) {
+        rtamd::set_last_error(std::string(what) + ": " + msg);
+        return rc;
+    };
+    if (!s) return fail("scene is NULL", RT_ERR_INVALID_ARG);
+    if (flags & ~(RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH))
+        return fail("unknown flag bits", RT_ERR_INVALID_ARG);
+    {
+        const int rv = rtamd::check_query_flags(flags);
+        if (rv != RT_OK) return rv;
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->n_gpus = 1;
+    }
+    if (n == 0) return RT_OK;
+    if (!rays) return fail("rays is NULL", RT_ERR_INVALID_ARG);
+    if (kind == rtamd::kQueryIsect ? !hits : !mask) return fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
+    const rt_scene_desc& d = *rt_scene_get_desc(s);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    Workspace& ws = workspace(dev);
+    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
+    // whatever happens below, nothing of this call is left queued on st when
+    // the lock goes (the next frame resets the staging arena the scene upload
+    // reads, and reuses the chunk buffers); declared after the lock: runs first
+    struct Drain {
+        hipStream_t st;
+        ~Drain() { (void)hipStreamSynchronize(st); }
+    } drain{st};
+    ws.up.reset();   // (the previous frame's or query's uploads completed)
+    {
+        const int rv = scene_resident(ws, s, d, false, st);
+        if (rv != RT_OK) return rv;
+    }
+    rtamd::KernelVariant kv;
+    {
+        const int rv = rtamd::pick_query_variant(ws.sc.cs, d, flags, &kv);
+        if (rv != RT_OK) return rv;
+    }
+    SceneView S;
+    scene_view(ws, d, flags, false, S);
+    S.n_chunks = 0;   // (the flat object list)
+    if (!ws.ev[0]) {
+        rtamd::SetupTimer tm(rtamd::kSetupStreams);
+        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
+    }
+    const bool isect = kind == rtamd::kQueryIsect;
+    const size_t chunk = host ? std::min(n, kQueryChunkRays) : n;
+    if (host) {
+        HIP_TRY(ws.q_rays.ensure(chunk * sizeof(rt_ray)));
+        if (isect) HIP_TRY(ws.q_hits.ensure(chunk * sizeof(rt_hit)));
+        if (!isect || mask) HIP_TRY(ws.q_mask.ensure(chunk));
+    }
+    double ms_kernel = 0.0;
+    for (size_t c0 = 0; c0 < n; c0 += chunk) {
+        const size_t cn = std::min(chunk, n - c0);
+        const rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays + c0;
+        rt_hit* d_hits = !isect ? nullptr : host ? ws.q_hits.as<rt_hit>() : hits + c0;
+        uint8_t* d_mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask + c0;
+        if (host) HIP_TRY(hipMemcpyAsync(ws.q_rays.p, rays + c0, cn * sizeof(rt_ray), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ws.ev[1], st));
+        for (size_t l0 = 0; l0 < cn; l0 += kQueryLaunchRays) {
+            QueryParams P;
+            P.n = std::min(kQueryLaunchRays, cn - l0);
+            P.rays = d_rays + l0;
+            P.hits = d_hits ? d_hits + l0 : nullptr;
+            P.mask = d_mask ? d_mask + l0 : nullptr;
+            HIP_TRY(rtamd::launch_query(kv, kind, st, S, P));
+        }
+        HIP_TRY(hipEventRecord(ws.ev[2], st));
+        if (host) {
+            if (isect) HIP_TRY(hipMemcpyAsync(hits + c0, d_hits, cn * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+            if (mask) HIP_TRY(hipMemcpyAsync(mask + c0, d_mask, cn, hipMemcpyDeviceToHost, st));
+        }
+        // (the chunk buffers and the events are reused by the next chunk)
+        HIP_TRY(hipStreamSynchronize(st));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) ms_kernel += ms;
+    }
+    if (stats) {
+        (isect ? stats->rays_intersect : stats->rays_occluded) = n;
+        stats->rays_traced = n;
+        stats->ms_kernel = ms_kernel;
+        stats->ms_total = ms_since(t_start);
+    }
+    return RT_OK;
+}
+
 }  // namespace
 
 void rtamd::set_workspace_slot(int slot) { t_ws_slot = slot; }
@@ -869,7 +999,8 @@ int rtamd::release_device_workspaces(int min_slot) {
                         &w->lwrec, &w->lgb, &w->fold,
                         &w->wobjs, &w->wctab, &w->worig, &w->wchunk,
                         &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->rows, &w->jit, &w->ckpt,
-                        &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime})
+                        &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime,
+                        &w->q_rays, &w->q_hits, &w->q_mask})
             b->release();
         w->jtab.release();
         w->rows_cached.clear();
@@ -1030,6 +1161,30 @@ extern "C" int rt_render(const rt_scene* s, int W, int H, int mode, int flags, d
         stats->ms_total = std::chrono::duration<double, std::milli>(t2 - t0).count();
     }
     return RT_OK;
+}
+
+extern "C" int rt_query_intersect(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, rt_hit* hits_host,
+                                  uint8_t* hit_mask_host, rt_stats* stats) {
+    return query_impl("rt_query_intersect", s, rtamd::kQueryIsect, rays_host, n, flags, hits_host, hit_mask_host, true,
+                      nullptr, stats);
+}
+
+extern "C" int rt_query_occluded(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, uint8_t* occluded_host,
+                                 rt_stats* stats) {
+    return query_impl("rt_query_occluded", s, rtamd::kQueryOccl, rays_host, n, flags, nullptr, occluded_host, true,
+                      nullptr, stats);
+}
+
+extern "C" int rt_query_intersect_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, rt_hit* hits_dev,
+                                         uint8_t* hit_mask_dev, void* hip_stream, rt_stats* stats) {
+    return query_impl("rt_query_intersect_device", s, rtamd::kQueryIsect, rays_dev, n, flags, hits_dev, hit_mask_dev,
+                      false, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_query_occluded_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags,
+                                        uint8_t* occluded_dev, void* hip_stream, rt_stats* stats) {
+    return query_impl("rt_query_occluded_device", s, rtamd::kQueryOccl, rays_dev, n, flags, nullptr, occluded_dev, false,
+                      (hipStream_t)hip_stream, stats);
 }
 
 extern "C" int rt_scatter_rows_device(const double* src_dev, const int32_t* rows_dev, int n_rows, int W,

@@ -141,6 +141,23 @@ extern "C" int rt_test_kernel_name(const rt_scene* s, int mode, int flags, char*
     return RT_OK;
 }
 
+extern "C" int rt_test_query_kernel_name(const rt_scene* s, int kind, int flags, char* out, int cap) {
+    if (!s || !out || cap <= 0 || (kind != rtamd::kQueryIsect && kind != rtamd::kQueryOccl)) return RT_ERR_INVALID_ARG;
+    rtamd::KernelVariant v;
+    try {
+        const rt_scene_desc& d = *rt_scene_get_desc(s);
+        const int rc = rtamd::pick_query_variant(rtamd::compile_scene(d), d, flags, &v);
+        if (rc != RT_OK) return rc;
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("scene compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+    const rtamd::KernelEntry k = rtamd::query_kernel(v, kind);
+    if (!k.name) { rtamd::set_last_error("rt_test_query_kernel_name: no kernel for this variant"); return RT_ERR_UNSUPPORTED; }
+    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
+    return RT_OK;
+}
+
 extern "C" int rt_test_kernel_info(const rt_scene* s, int mode, int flags, int32_t* out) {
     if (!s || !out) return RT_ERR_INVALID_ARG;
     int ndev = 0;

@@ -28,6 +28,29 @@ bool plain_scene(const CompiledScene& cs) {
             return false;
     return true;
 }
+
+// Stack tiers: the common kernels, else the big-stack build (rtdb, *big), else
+// refuse.  frames: the reflection / refraction frames the trace needs.
+int stack_tier(const CompiledScene& cs, const rt_scene_desc& d, int frames, bool fp32, bool* big) {
+    *big = false;
+    if (cs.max_ray_depth > kMaxRayStack || cs.max_ivl_depth > kMaxIvlSpill + 2 || frames > kMaxDepth) {
+        if (cs.max_ray_depth > kBigRayStack || cs.max_ivl_depth > kBigIvlSpill + 2 || frames > kBigDepth) {
+            set_last_error("scene exceeds the device stacks: transform nesting inside CSG operands " +
+                           std::to_string(cs.max_ray_depth) + " (max " + std::to_string(kBigRayStack) +
+                           "), CSG operand depth " + std::to_string(cs.max_ivl_depth) + " (max " +
+                           std::to_string(kBigIvlSpill + 2) + "), medium.recursion " +
+                           std::to_string(d.recursion_limit) + " with reflection/refraction (max " +
+                           std::to_string(kBigDepth + 1) + ")");
+            return RT_ERR_UNSUPPORTED;
+        }
+        if (fp32) {
+            set_last_error("the FP32 fast path has only the common device stacks; render this scene in FP64");
+            return RT_ERR_UNSUPPORTED;
+        }
+        *big = true;
+    }
+    return RT_OK;
+}
 }  // namespace
 
 // ------------------------------------------------------------ kernel variant
@@ -48,24 +71,11 @@ int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int 
     for (int i = 0; i < d.n_materials; ++i)
         if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) v.secondary = true;
     if (d.recursion_limit < 2) v.secondary = false;   // depth < limit-1 never holds (tracer.cpp:38,51)
-    // Stack tiers: the common kernels, else the big-stack build (rtdb), else refuse.
     const int frames = (v.secondary && mode == RT_MODE_STANDARD) ? d.recursion_limit - 1 : 0;
     bool big = false;
-    if (cs.max_ray_depth > kMaxRayStack || cs.max_ivl_depth > kMaxIvlSpill + 2 || frames > kMaxDepth) {
-        if (cs.max_ray_depth > kBigRayStack || cs.max_ivl_depth > kBigIvlSpill + 2 || frames > kBigDepth) {
-            set_last_error("scene exceeds the device stacks: transform nesting inside CSG operands " +
-                           std::to_string(cs.max_ray_depth) + " (max " + std::to_string(kBigRayStack) +
-                           "), CSG operand depth " + std::to_string(cs.max_ivl_depth) + " (max " +
-                           std::to_string(kBigIvlSpill + 2) + "), medium.recursion " +
-                           std::to_string(d.recursion_limit) + " with reflection/refraction (max " +
-                           std::to_string(kBigDepth + 1) + ")");
-            return RT_ERR_UNSUPPORTED;
-        }
-        if (fp32) {
-            set_last_error("the FP32 fast path has only the common device stacks; render this scene in FP64");
-            return RT_ERR_UNSUPPORTED;
-        }
-        big = true;
+    {
+        const int rc = stack_tier(cs, d, frames, fp32, &big);
+        if (rc != RT_OK) return rc;
     }
     v.ns = big ? KernelVariant::kRtdb : fp32 ? KernelVariant::kRtf : KernelVariant::kRtd;
     v.count_ops = (flags & RT_FLAG_COUNT_OPS) != 0;
@@ -88,6 +98,36 @@ int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int 
         const bool general = mode == RT_MODE_STANDARD && v.secondary && v.wv == 0;
         v.plain = !general && !fp32 && !v.count_ops && plain_on && plain_scene(cs);
     }
+    *out = v;
+    return RT_OK;
+}
+
+int check_query_flags(int flags) {
+    if (flags & RT_FLAG_FP32) {
+        set_last_error("ray queries have no FP32 kernels (RT_FLAG_FP32): they run the FP64 parity path");
+        return RT_ERR_UNSUPPORTED;
+    }
+    if (flags & RT_FLAG_COUNT_OPS) {
+        set_last_error("ray queries do not count ops (RT_FLAG_COUNT_OPS)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    return RT_OK;
+}
+
+int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out) {
+    int rc = check_query_flags(flags);
+    if (rc != RT_OK) return rc;
+    KernelVariant v;
+    bool big = false;
+    rc = stack_tier(cs, d, 0, false, &big);
+    if (rc != RT_OK) return rc;
+    v.ns = big ? KernelVariant::kRtdb : KernelVariant::kRtd;
+    // (as pick_variant: the big-stack build has only the general variant, eager
+    // scenes always use D, scenes with directional lights take the D variants)
+    v.eager = big || cs.has_eager;
+    v.deep = v.eager || cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
+    static const bool plain_on = env_on("RT_PLAIN");
+    v.plain = !v.deep && plain_on && plain_scene(cs);
     *out = v;
     return RT_OK;
 }

@@ -60,6 +60,17 @@ const char* variant_ns_name(int ns);   // "rtd" / "rtf" / "rtdb"
 int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int flags, bool bvh_enabled,
                  KernelVariant* out);
 
+// The variant a ray query (rt_query_intersect / rt_query_occluded) of (scene,
+// flags) launches: pick_variant's stack tiers (no recursion frames: a query
+// traces one ray) and its eager / deep / plain rules, always with per-lane
+// culls (wv = 0: a query's rays are arbitrary, the wave-level culls and the
+// wave BVH bound a pixel tile's) and never secondary.  RT_OK, or
+// RT_ERR_UNSUPPORTED with the message set: RT_FLAG_FP32 or RT_FLAG_COUNT_OPS
+// (queries are FP64 and uncounted: check_query_flags, which a query asks
+// before anything else), or a scene beyond the big stacks.
+int check_query_flags(int flags);
+int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
+
 // ----------------------------------------------------------------- dist plan
 constexpr int kChunks = 4;   // pipeline units per rank (chunk k gathered while k+1 is traced)
 // Paper frames gather one code byte per pixel, so their chunks hide little

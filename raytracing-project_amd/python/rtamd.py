@@ -9,6 +9,9 @@ mirror the reference's interface for the hot path:
   (raytracer/src/json_loader.cpp:458-503)
 * ``Tracer(scene, width, height, mode).render()`` -> ``Tracer::render``
   (raytracer/src/tracer.h:18-35, tracer.cpp:247-305)
+* ``query_intersect(scene, origins, dirs, ...)`` / ``query_occluded`` ->
+  ``Scene::intersect`` / ``Scene::occluded`` for a batch of rays
+  (raytracer/src/scene.cpp:10-24, 33-42)
 
 The GPU path fails loudly (RuntimeError) when librtamd.so is missing or no HIP
 device is present; there is no CPU fallback.  The CPU oracle (oracle/) and the
@@ -34,6 +37,8 @@ RT_MODE_STANDARD = 0
 RT_MODE_PAPER = 1
 RT_OK = 0
 RT_ERR_INVALID_ARG = -1
+RT_ERR_HIP = -5
+RT_ERR_UNSUPPORTED = -6
 RT_ERR_NO_DEVICE = -7
 RT_FLAG_NONE = 0
 RT_FLAG_COUNT_OPS = 1
@@ -110,6 +115,22 @@ class OracleHit(C.Structure):
         return (self.t, tuple(self.p), tuple(self.n), self.mat, self.front_face)
 
 
+class Ray(C.Structure):
+    """rt_ray: Ray(o, d) (d is normalised on the device, core.h:278) and its range."""
+    _fields_ = [("o", C.c_double * 3), ("d", C.c_double * 3), ("tmin", C.c_double), ("tmax", C.c_double)]
+
+
+class Hit(C.Structure):
+    """rt_hit (the layout of oracle_hit); a miss: mat -1, every other field 0."""
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("n", C.c_double * 3), ("mat", C.c_int32),
+                ("front_face", C.c_int32)]
+
+
+# the same records as numpy dtypes (64 B each)
+RAY_DTYPE = np.dtype([("o", "<f8", (3,)), ("d", "<f8", (3,)), ("tmin", "<f8"), ("tmax", "<f8")])
+HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("n", "<f8", (3,)), ("mat", "<i4"), ("front_face", "<i4")])
+assert RAY_DTYPE.itemsize == C.sizeof(Ray) == 64 and HIT_DTYPE.itemsize == C.sizeof(Hit) == 64
+
 _dp = C.POINTER(C.c_double)
 
 
@@ -162,6 +183,16 @@ def amd_lib():
             lib.rt_frame_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
             lib.rt_frame_end.argtypes = [C.c_void_p, C.POINTER(Stats)]
         lib.rt_framebuffer_to_rgb8_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_query_intersect"):   # (absent only in RTAMD_LIB builds of older sources)
+            lib.rt_query_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.POINTER(Stats)]
+            lib.rt_query_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                              C.POINTER(Stats)]
+            lib.rt_query_intersect_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.rt_query_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(Stats)]
+            lib.rt_test_query_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
         lib.rt_device_count.restype = C.c_int
         lib.rt_render_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                         C.POINTER(Stats)]
@@ -467,6 +498,74 @@ class Tracer:
         if rc != RT_OK:
             raise RTError(rc, last_error())
         return fb
+
+
+def make_rays(origins, dirs, tmin=1e-4, tmax=np.inf) -> np.ndarray:
+    """An rt_ray array (RAY_DTYPE) from (n, 3) origins and directions; scalar
+    tmin / tmax broadcast.  Directions need not be normalised."""
+    o = np.asarray(origins, dtype=np.float64)
+    d = np.asarray(dirs, dtype=np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and dirs must both be (n, 3) arrays, got {o.shape} and {d.shape}")
+    rays = np.empty(o.shape[0], dtype=RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float64), (o.shape[0],))
+    rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float64), (o.shape[0],))
+    return rays
+
+
+@dataclass
+class QueryHits:
+    """query_intersect's result: `records` is the rt_hit array (HIT_DTYPE; a
+    miss has mat -1 and zeros), `hit` the hit flags as bools."""
+    records: np.ndarray
+    hit: np.ndarray
+
+    t = property(lambda self: self.records["t"])
+    p = property(lambda self: self.records["p"])
+    n = property(lambda self: self.records["n"])
+    mat = property(lambda self: self.records["mat"])
+    front_face = property(lambda self: self.records["front_face"])
+
+    def __len__(self):
+        return len(self.records)
+
+
+def query_intersect(scene: Scene, origins, dirs, tmin=1e-4, tmax=np.inf, flags: int = RT_FLAG_NONE,
+                    stats: Stats | None = None) -> QueryHits:
+    """rt_query_intersect: Scene::intersect (closest hit) of every ray."""
+    rays = make_rays(origins, dirs, tmin, tmax)
+    n = len(rays)
+    hits = np.zeros(n, dtype=HIT_DTYPE)
+    mask = np.zeros(n, dtype=np.uint8)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_intersect(scene.handle, rays.ctypes.data_as(C.c_void_p), n, flags,
+                                      hits.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return QueryHits(hits, mask.astype(bool))
+
+
+def query_occluded(scene: Scene, origins, dirs, tmin=1e-4, tmax=np.inf, flags: int = RT_FLAG_NONE,
+                   stats: Stats | None = None) -> np.ndarray:
+    """rt_query_occluded: Scene::occluded (any hit in [tmin, tmax]) of every ray, as bools."""
+    rays = make_rays(origins, dirs, tmin, tmax)
+    n = len(rays)
+    occ = np.zeros(n, dtype=np.uint8)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_occluded(scene.handle, rays.ctypes.data_as(C.c_void_p), n, flags,
+                                     occ.ctypes.data_as(C.c_void_p), C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return occ.astype(bool)
+
+
+def query_kernel_name(scene: Scene, kind: int, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
+    """rt_test_query_kernel_name: (status, "ns::kernel") of the kernel a query
+    of kind 0 (intersect) / 1 (occluded) launches.  Host only."""
+    buf = C.create_string_buffer(160)
+    rc = amd_lib().rt_test_query_kernel_name(scene.handle, kind, flags, buf, 160)
+    return rc, buf.value.decode()
 
 
 def render_multi(scene: Scene, width: int, height: int, mode: int, n_gpus: int, flags: int = RT_FLAG_NONE,

@@ -34,6 +34,7 @@ static int check_file(const char* path, const char* png_out) {
         for (int flags : {0, (int)RT_FLAG_COUNT_OPS, (int)RT_FLAG_NO_CULL, (int)RT_FLAG_NO_BVH, (int)RT_FLAG_FP32}) {
             rtamd::KernelVariant v;
             (void)rtamd::pick_variant(cs, *d, mode, flags, true, &v);   // (a refusal is a valid outcome)
+            if (mode == 0) (void)rtamd::pick_query_variant(cs, *d, flags, &v);   // (the ray queries' kernel choice)
         }
     int W = rt_camera_width(&d->camera), H = rt_camera_height(&d->camera);
     if (W > 64) W = 64;
