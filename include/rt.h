@@ -393,7 +393,9 @@ typedef struct rt_hit {        /* 64 B; geometry.h:25-46 Hit */
     double t;
     double p[3];
     double n[3];
-    int32_t mat;               /* material index; -1 on a miss (every other field 0) */
+    int32_t mat;               /* material index; -1 for a hit on a null material (rt_node.mat
+                                  == -1, the reference's mat{nullptr}: t, p, n are the hit's)
+                                  and on a miss (every other field 0): hit_mask tells them apart */
     int32_t front_face;
 } rt_hit;
 /* hits_host[i] = Scene::intersect(rays_host[i]) for i < n; hit_mask_host (may

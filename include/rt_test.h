@@ -68,6 +68,18 @@ int rt_test_query_kernel_name(const struct rt_scene* s, int kind, int flags, cha
  * two to be bit-identical. */
 int rt_test_div3(const double* a_host, const double* b_host, int n, double* div3_host, double* plain_host);
 
+/* GPU: out_host[i] = pow_spec(x_host[i], y_host[i]), the device code's own
+ * std::pow(rdotv, shininess) of the specular term (rt_device.hpp pow_spec,
+ * shading.cpp:124), one lane per element, 256-thread blocks in input order (so
+ * the caller decides which exponents share a wave).  Contract: for an integer
+ * y in [0, 1023] the result is the correctly rounded x^y wherever that is
+ * >= 2^-1000 (below: a value in [0, 2^-999]), and exactly 1.0 for y == 0
+ * whatever x is (NaN included); every other y is the device library's pow
+ * (pow_general), within 1e-12 relative of the exact power, with pow(0, y > 0)
+ * = 0, pow(0, y < 0) = +inf and pow(1, y) = 1 exactly.  x >= 0 (shade() clamps
+ * rdotv at 0).  Returns an rt_status. */
+int rt_test_pow_spec(const double* x_host, const double* y_host, int n, double* out_host);
+
 /* Host only: the precomputed mt19937 tree jump polynomials in `path` (the
  * build's lib/mt19937_tree.polys, read by the jitter generator) against the
  * same polynomials computed in this process, first `levels` levels.

@@ -896,6 +896,23 @@ int oracle_scene_occluded(const rt_scene_desc* d, const double o[3], const doubl
     return scene_occluded(&c, &r, tmin, tmax);
 }
 
+int oracle_scene_occluded_batch(const rt_scene_desc* d, int n, const double* o, const double* dir, const double* tmin,
+                                const double* tmax, uint8_t* out) {
+    for (int i = 0; i < n; ++i) out[i] = (uint8_t)oracle_scene_occluded(d, o + 3 * i, dir + 3 * i, tmin[i], tmax[i]);
+    return 0;
+}
+
+int oracle_primary_hits(const rt_scene_desc* d, int W, int H, double* dirs, oracle_hit* hits, uint8_t* ok) {
+    for (int j = 0; j < H; ++j)
+        for (int i = 0; i < W; ++i) {
+            const size_t k = (size_t)j * W + i;
+            double o[3];
+            oracle_camera_ray(d, i, j, 0.0, 0.0, 0, o, dirs + 3 * k);
+            ok[k] = (uint8_t)oracle_scene_intersect(d, o, dirs + 3 * k, 1e-4, kINF, &hits[k]);
+        }
+    return 0;
+}
+
 void oracle_camera_ray(const rt_scene_desc* d, int i, int j, double dx, double dy, int subpixel, double o[3],
                        double dir[3]) {
     Ray r = subpixel ? generate_ray_subpixel(&d->camera, i, j, dx, dy) : generate_ray(&d->camera, i, j);

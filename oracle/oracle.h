@@ -56,6 +56,14 @@ int oracle_scene_intersect(const rt_scene_desc* d, const double o[3], const doub
 int oracle_scene_occluded(const rt_scene_desc* d, const double o[3], const double dir[3],
                           double tmin, double tmax);
 
+/* oracle_scene_occluded for n rays (o, dir: 3n doubles; tmin, tmax: n). */
+int oracle_scene_occluded_batch(const rt_scene_desc* d, int n, const double* o, const double* dir, const double* tmin,
+                                const double* tmax, uint8_t* out);
+/* The pixel-centre primary hit of every pixel of the W x H frame, pixel (i, j)
+ * at index j*W + i: Camera::generate_ray(i, j) -> dirs, Scene::intersect(r,
+ * 1e-4, inf) -> ok, hits. */
+int oracle_primary_hits(const rt_scene_desc* d, int W, int H, double* dirs, oracle_hit* hits, uint8_t* ok);
+
 /* Camera::generate_ray (subpixel=0) / generate_ray_subpixel (subpixel=1). */
 void oracle_camera_ray(const rt_scene_desc* d, int i, int j, double dx, double dy, int subpixel,
                        double o[3], double dir[3]);

@@ -68,13 +68,15 @@ std::shared_ptr<Primitive> build_node(Built& b, const rt_scene_desc* d, int idx)
     if (b.nodes[idx]) return b.nodes[idx];
     const rt_node& n = d->nodes[idx];
     std::shared_ptr<Primitive> p;
+    // mat -1 is the reference's own default, a null material (geometry.h: mat{nullptr})
+    const Material* leaf_mat = n.mat >= 0 ? b.mats[n.mat].get() : nullptr;
     switch (n.kind) {
         case RT_NODE_SPHERE:
-            p = std::make_shared<Sphere>(Point3(n.v[0], n.v[1], n.v[2]), n.v[3], b.mats[n.mat].get());
+            p = std::make_shared<Sphere>(Point3(n.v[0], n.v[1], n.v[2]), n.v[3], leaf_mat);
             break;
         case RT_NODE_HALFSPACE:
             p = std::make_shared<HalfSpace>(Point3(n.v[0], n.v[1], n.v[2]), Dir3(n.aux[0], n.aux[1], n.aux[2]),
-                                            b.mats[n.mat].get());
+                                            leaf_mat);
             break;
         case RT_NODE_POKEBALL: {
             auto pb = std::make_shared<Pokeball>(

@@ -20,7 +20,37 @@ __global__ void k_test_div3(const double* a, const double* b, int n, double* o3,
     op[3 * i + 1] = a[3 * i + 1] / b[i];
     op[3 * i + 2] = a[3 * i + 2] / b[i];
 }
+// pow_spec (rt_device.hpp), the specular term's power, on caller-given (x, y):
+// integer and other exponents may share a wave, as materials do in shade().
+__global__ void k_test_pow_spec(const double* x, const double* y, int n, double* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = rtd::pow_spec(x[i], y[i]);
+}
 }  // namespace
+
+extern "C" int rt_test_pow_spec(const double* x_host, const double* y_host, int n, double* out_host) {
+    if (n <= 0 || !x_host || !y_host || !out_host) return RT_ERR_INVALID_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RT_ERR_NO_DEVICE;
+    double *x = nullptr, *y = nullptr, *o = nullptr;
+    const size_t nb = (size_t)n * sizeof(double);
+    int rc = RT_OK;
+    if (hipMalloc(&x, nb) != hipSuccess || hipMalloc(&y, nb) != hipSuccess || hipMalloc(&o, nb) != hipSuccess)
+        rc = RT_ERR_HIP;
+    if (rc == RT_OK && (hipMemcpy(x, x_host, nb, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(y, y_host, nb, hipMemcpyHostToDevice) != hipSuccess))
+        rc = RT_ERR_HIP;
+    if (rc == RT_OK) {
+        hipLaunchKernelGGL(k_test_pow_spec, dim3((n + 255) / 256), dim3(256), 0, nullptr, x, y, n, o);
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out_host, o, nb, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = RT_ERR_HIP;
+    }
+    if (x) (void)hipFree(x);
+    if (y) (void)hipFree(y);
+    if (o) (void)hipFree(o);
+    return rc;
+}
 
 extern "C" int rt_test_div3(const double* a_host, const double* b_host, int n, double* div3_host, double* plain_host) {
     if (n <= 0 || !a_host || !b_host || !div3_host || !plain_host) return RT_ERR_INVALID_ARG;

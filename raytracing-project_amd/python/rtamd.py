@@ -406,6 +406,75 @@ def with_dir_lights(scene: Scene, lights) -> Scene:
     return scene_from_desc(d)
 
 
+def with_null_materials(scene: Scene, node_indices) -> Scene:
+    """Copy of `scene` whose sphere / half-space nodes `node_indices` have no
+    material (rt_node.mat = -1): the reference's default mat{nullptr}
+    (geometry.h), which its JSON schema cannot spell; reachable here through
+    rt_scene_from_desc as there through the constructors."""
+    d = SceneDesc.from_buffer_copy(scene.desc)
+    nodes = (Node * d.n_nodes)()
+    C.memmove(nodes, d.nodes, C.sizeof(Node) * d.n_nodes)
+    for i in node_indices:
+        i = int(i)
+        if not 0 <= i < d.n_nodes or nodes[i].kind not in (NODE_SPHERE, NODE_HALFSPACE):
+            raise ValueError(f"node {i} is not a sphere or half-space of this scene")
+        nodes[i].mat = -1
+    d.nodes = C.cast(nodes, C.POINTER(Node))
+    return scene_from_desc(d)
+
+
+def with_material_fields(scene: Scene, changes: dict) -> Scene:
+    """Copy of `scene` with Material fields set, {material index: {field:
+    value}}: values the JSON schema cannot give (kd is 1 for every colour
+    block, json_loader.cpp:83-123)."""
+    d = SceneDesc.from_buffer_copy(scene.desc)
+    mats = (Material * d.n_materials)()
+    C.memmove(mats, d.materials, C.sizeof(Material) * d.n_materials)
+    for i, fields in changes.items():
+        if not 0 <= int(i) < d.n_materials:
+            raise ValueError(f"no material {i} in this scene")
+        for k, v in fields.items():
+            setattr(mats[int(i)], k, float(v))
+    d.materials = C.cast(mats, C.POINTER(Material))
+    return scene_from_desc(d)
+
+
+def sphere_nodes_at(scene: Scene, centres) -> list[int]:
+    """Node index of the sphere node at each of `centres` (exact coordinates)."""
+    d = scene.desc
+    out = []
+    for c in centres:
+        found = [i for i in range(d.n_nodes)
+                 if d.nodes[i].kind == NODE_SPHERE and tuple(d.nodes[i].v[0:3]) == tuple(float(x) for x in c)]
+        if len(found) != 1:
+            raise ValueError(f"{len(found)} sphere nodes at {list(c)}")
+        out.append(found[0])
+    return out
+
+
+def kernel_name(scene: Scene, mode: int, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
+    """rt_test_kernel_name: (status, "ns::kernel") of the trace kernel a frame
+    of this scene, mode and flags launches.  Host only."""
+    lib = amd_lib()
+    lib.rt_test_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(160)
+    rc = lib.rt_test_kernel_name(scene.handle, mode, flags, buf, 160)
+    return rc, buf.value.decode()
+
+
+def pow_spec(x, y) -> np.ndarray:
+    """rt_test_pow_spec: the device's pow_spec(x[i], y[i]) (rt_device.hpp)."""
+    lib = amd_lib()
+    lib.rt_test_pow_spec.argtypes = [_dp, _dp, C.c_int, _dp]
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    assert x.shape == y.shape and x.ndim == 1
+    out = np.zeros_like(x)
+    _ok(lib.rt_test_pow_spec(x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), len(x), out.ctypes.data_as(_dp)),
+        "rt_test_pow_spec")
+    return out
+
+
 def device_count() -> int:
     return int(amd_lib().rt_device_count())
 
@@ -692,6 +761,41 @@ def oracle_render(scene: Scene, width: int, height: int, mode: int, row0: int = 
     if rc != 0:
         raise RuntimeError("oracle_render_rows failed")
     return fb, st
+
+
+def oracle_primary_hits(scene: Scene) -> np.ndarray:
+    """The pixel-centre primary hits of the frame (Camera::generate_ray +
+    Scene::intersect(r, 1e-4, inf) through the oracle), one record per pixel:
+    hit (bool), d (the ray direction) and the Hit fields.  TEST ONLY."""
+    lib = oracle_lib()
+    W, H = scene.width, scene.height
+    dirs = np.zeros((W * H, 3))
+    hits = np.zeros(W * H, dtype=HIT_DTYPE)
+    ok = np.zeros(W * H, dtype=np.uint8)
+    lib.oracle_primary_hits.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_int, _dp, C.c_void_p, C.c_void_p]
+    lib.oracle_primary_hits(scene.desc_ptr, W, H, dirs.ctypes.data_as(_dp), hits.ctypes.data_as(C.c_void_p),
+                            ok.ctypes.data_as(C.c_void_p))
+    rec = np.zeros(W * H, dtype=[("hit", "?"), ("d", "<f8", (3,)), ("t", "<f8"), ("p", "<f8", (3,)),
+                                 ("n", "<f8", (3,)), ("mat", "<i4"), ("front_face", "<i4")])
+    rec["hit"], rec["d"] = ok.astype(bool), dirs
+    for f in ("t", "p", "n", "mat", "front_face"):
+        rec[f] = hits[f]
+    return rec
+
+
+def oracle_occluded(scene: Scene, origins, dirs, tmin, tmax) -> np.ndarray:
+    """Scene::occluded of every ray through the oracle, as bools.  TEST ONLY."""
+    lib = oracle_lib()
+    o = np.ascontiguousarray(origins, dtype=np.float64)
+    d = np.ascontiguousarray(dirs, dtype=np.float64)
+    n = len(o)
+    t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, dtype=np.float64), (n,)))
+    t1 = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float64), (n,)))
+    out = np.zeros(n, dtype=np.uint8)
+    lib.oracle_scene_occluded_batch.argtypes = [C.POINTER(SceneDesc), C.c_int, _dp, _dp, _dp, _dp, C.c_void_p]
+    lib.oracle_scene_occluded_batch(scene.desc_ptr, n, o.ctypes.data_as(_dp), d.ctypes.data_as(_dp),
+                                    t0.ctypes.data_as(_dp), t1.ctypes.data_as(_dp), out.ctypes.data_as(C.c_void_p))
+    return out.astype(bool)
 
 
 def ref_render(scene: Scene, width: int, height: int, mode: int):

@@ -510,3 +510,322 @@ def crowd_scene(seed: int, n_objects: int = 150, dpi: int = 16) -> dict:
     lights = [{"position": [rnd.uniform(-6, 6), rnd.uniform(3, 7), rnd.uniform(-2, 6)],
                "intensity": [rnd.uniform(8, 25)] * 3} for _ in range(4)]
     return _base(objs, recursion=3, dpi=dpi, lights=lights)
+
+
+# ------------------------------------------------------------ shading scenes
+SHADING_LAYOUTS = ("few", "wave", "csg", "xform", "bvh")
+SHADING_EXPONENTS = (0, 1, 2, 3, 5, 7, 127, 255, 1000, 1023, 1024, 2000, 12.5, 0.5, -2)
+ONE_OF_65 = (0, 4, 5, 31, 32, 36, 37, 63, 64)
+_FLOOR_Y = -1.2
+
+
+def _sph(p, r, col, **kw):
+    s = {"position": [float(v) for v in p], "radius": r, "color": col}
+    s.update(kw)
+    return {"sphere": s}
+
+
+def _floor(y=_FLOOR_Y, **kw):
+    return {"halfSpace": {"position": [0, y, 0], "normal": [0, 1, 0], "color": _mat([0.5, 0.6, 0.5], **kw)}}
+
+
+def shading_layout(layout: str) -> list:
+    """The object sets that decide which kernel's shade() runs (frame_plan.cpp
+    pick_variant): few (< 4 bounded objects: no wave culls), wave (>= 4: wave
+    culls, plain kernels), csg (+ a leaf-only CSG and a pokeball: non-plain),
+    xform (+ a transform inside a CSG operand: eager, the D variant), bvh (a
+    lattice of more than 256 spheres: the wave BVH)."""
+    balls = [
+        _sph([-1.3, -0.5, -1.0], 0.7, _mat([0.8, 0.3, 0.2])),
+        _sph([0.9, -0.4, -1.6], 0.8, _mat([0.2, 0.5, 0.8], shininess=12)),
+        _sph([-0.2, 0.7, -2.6], 0.6, _mat([0.3, 0.8, 0.3], reflected=[0.5, 0.5, 0.5])),
+        _sph([1.7, 0.7, -0.8], 0.4, _mat([0.8, 0.8, 0.2], refracted=[0.6, 0.6, 0.6]), index=1.5),
+        _sph([-1.7, 0.9, -1.8], 0.45, _mat([0.7, 0.3, 0.7], shininess=5)),
+    ]
+    if layout == "few":
+        return [_floor()] + balls[:2]
+    if layout == "wave":
+        return [_floor()] + balls
+    diff = {"difference": [_sph([0.0, -0.7, -0.1], 0.5, _mat([0.9, 0.6, 0.2])),
+                           _sph([0.1, -0.5, 0.3], 0.35, _mat([0.2, 0.2, 0.9]))]}
+    poke = {"pokeball": {"position": [-0.6, 1.5, -1.2], "radius": 0.35, "button_dir": [0.2, 0.1, 1.0]}}
+    if layout == "csg":
+        return [_floor()] + balls + [diff, poke]
+    if layout == "xform":
+        xf = {"union": [{"translation": {"factors": [0.9, 1.5, -1.4], "subject":
+                                          _sph([0, 0, 0], 0.35, _mat([0.3, 0.7, 0.9]))}},
+                        _sph([1.25, 1.7, -1.3], 0.25, _mat([0.9, 0.5, 0.1]))]}
+        return [_floor()] + balls + [diff, poke, xf]
+    if layout == "bvh":
+        objs = [_floor()]
+        for k in range(17 * 16):
+            i, j = k % 17, k // 17
+            m = _mat([(k % 7) / 7.0, (k % 5) / 5.0, (k % 3) / 3.0], shininess=8 + 4 * (k % 5))
+            if k % 5 == 0:
+                m["reflected"] = [0.4, 0.4, 0.4]
+            elif k % 7 == 0:
+                m["refracted"] = [0.5, 0.5, 0.5]
+            objs.append(_sph([-2.4 + 0.3 * i, -1.0 + 0.05 * (i % 3), -1.0 - 0.3 * j], 0.1 + 0.03 * ((i + j) % 3), m,
+                             index=1.5))
+        return objs
+    raise KeyError(layout)
+
+
+def ring_lights(n: int) -> list:
+    """n dim point lights on a golden-angle spiral above and around the layouts."""
+    out = []
+    for l in range(n):
+        a = 2.399963 * l
+        R = 2.0 + 3.0 * ((l * 5) % n) / n
+        out.append({"position": [R * math.cos(a), 4.0 + 2.0 * ((l * 7) % n) / n, -1.2 + R * math.sin(a)],
+                    "intensity": [0.35 + 0.25 * ((l * 3) % 7) / 6.0, 0.35 + 0.25 * ((l * 5) % 7) / 6.0,
+                                  0.35 + 0.25 * (l % 7) / 6.0]})
+    return out
+
+
+def _window(scene, points, size, dpi):
+    """Narrow the screen to a size[0] x size[1] window (in screen-plane units)
+    centred on the projection of `points` through the observer."""
+    scr = scene["screen"]
+    eye, z0 = scr["observer"], scr["position"][2]
+    px = []
+    for p in points:
+        f = (z0 - eye[2]) / (p[2] - eye[2])
+        px.append((eye[0] + (p[0] - eye[0]) * f, eye[1] + (p[1] - eye[1]) * f))
+    cx = sum(x for x, _ in px) / len(px)
+    cy = sum(y for _, y in px) / len(px)
+    # centre snapped to the pixel grid, so that width and height stay exact
+    cx, cy = round(cx * dpi) / dpi, round(cy * dpi) / dpi
+    scr["dpi"] = dpi
+    scr["dimensions"] = [size[0], size[1]]
+    scr["position"] = [cx - size[0] / 2.0, cy - size[1] / 2.0, z0]
+    return scene
+
+
+def shading_scenes(dpi: int = 24, detail: float = 1.0) -> dict[str, dict]:
+    """Shading and recursion inputs no other scene family has (shade() and the
+    trace loops of rt_device.hpp; shading.cpp:31-138, tracer.cpp:22-104), as
+    "<case>_<layout>" -> scene, over the layouts of shading_layout():
+      lights33/64/65  more point lights than one 32-light round of shade(), at
+                      the round edges
+      one65_kNN       the 65-light scene, every intensity 0 but light NN's
+      near_light      a light 0.05 above the floor (dist_squared <= 0.01), one
+                      0.3 off a sphere (max(0.5, distance)), one ordinary,
+                      on a screen narrowed around the two
+      far_skip        hits at t ~ 2000 (shadow_epsilon ~ 0.2) with lights 0.25
+                      off the surface: max_shadow_t <= shadow_epsilon
+      exponents       one sphere per shininess of SHADING_EXPONENTS (integers
+                      up to 1023, 1024, 2000, 12.5, 0.5, -2: pow(0, -2) = inf)
+      extremes        a light that saturates the 1.5 clamp, a negative
+                      intensity, albedo > 1, ks = 0, zero ambient, kd = 0
+      media           medium.index 1.33 around spheres of index 1.5, 1.33,
+                      1.0, one with kr and kt, one refractive CSG operand
+      null_mat        spheres without a material, bare and as a CSG operand
+    dpi scales every frame (24: at most 128 x 96 pixels, 256 x 192 for
+    exponents); detail scales the extra pixel density of the cases on a
+    narrowed screen (near_light, far_skip, exponents), which the tests need to
+    count branch hits and the fixtures do not.  Materials and nodes the JSON schema cannot spell are listed
+    by shading_patches() and applied by shading_load()."""
+    sc = {}
+
+    def put(name, objs, lights, recursion=3, scr_dpi=dpi):
+        sc[name] = _base(copy.deepcopy(objs), recursion=recursion, dpi=scr_dpi, lights=copy.deepcopy(lights))
+        return sc[name]
+
+    # ---- many lights
+    for n in (33, 64, 65):
+        for lay in SHADING_LAYOUTS:
+            if lay == "bvh" and n != 33:
+                continue
+            put(f"lights{n}_{lay}", shading_layout(lay), ring_lights(n))
+    for lay in ("wave", "csg"):
+        for k in ONE_OF_65:
+            lights = ring_lights(65)
+            for i, L in enumerate(lights):
+                if i != k:
+                    L["intensity"] = [0, 0, 0]
+            put(f"one65_k{k:02d}_{lay}", shading_layout(lay), lights, scr_dpi=max(1, dpi // 2))
+
+    # ---- near lights: A just above the floor, B 0.3 off a sphere's surface
+    ordinary = {"position": [3, 5, 4], "intensity": [12, 12, 12]}
+    for lay in ("few", "wave", "bvh"):
+        objs = shading_layout(lay)
+        s0 = objs[1]["sphere"]
+        c, r = s0["position"], s0["radius"]
+        u = [0.3, 0.3, 1.0]
+        un = math.sqrt(sum(v * v for v in u))
+        u = [v / un for v in u]
+        B = [c[i] + (r + 0.3) * u[i] for i in range(3)]
+        cap = [c[i] + r * u[i] for i in range(3)]
+        A = [cap[0] + 0.25, _FLOOR_Y + 0.05, cap[2] + 0.8]
+        lights = [{"position": A, "intensity": [0.02, 0.02, 0.015]}, {"position": B, "intensity": [0.2, 0.15, 0.2]},
+                  ordinary]
+        s = put(f"near_light_{lay}", objs, lights)
+        size = (1.2, 1.2) if lay != "bvh" else (0.6, 0.6)
+        px = int(detail * ((dpi * 10) // 3 if lay != "bvh" else (dpi * 20) // 3))
+        _window(s, [A, cap], size, px)
+
+    # ---- lights inside the shadow epsilon of a far hit
+    for lay in ("few", "wave"):
+        big = _sph([0, 0, -2100], 100.0, _mat([0.7, 0.6, 0.5]))
+        small = [_sph([1.5, 1.0, -1996.0], 0.5, _mat([0.2, 0.5, 0.9])),
+                 _sph([-2.0, 1.5, -1997.0], 0.6, _mat([0.9, 0.5, 0.2])),
+                 _sph([-1.0, -2.0, -1995.0], 0.4, _mat([0.3, 0.8, 0.3])),
+                 _sph([2.5, -1.5, -1998.0], 0.7, _mat([0.8, 0.3, 0.7]))]
+        objs = [_floor(-120.0), big] + (small[:1] if lay == "few" else small)
+        lights = []
+        for (x, y) in ((0.0, 0.0), (1.2, -0.6)):
+            z = math.sqrt(100.0 ** 2 - x * x - y * y)
+            nrm = [x / 100.0, y / 100.0, z / 100.0]
+            lights.append({"position": [x + 0.25 * nrm[0], y + 0.25 * nrm[1], -2100 + z + 0.25 * nrm[2]],
+                           "intensity": [0.05, 0.04, 0.03]})
+        lights.append({"position": [30, 40, -1950], "intensity": [600, 600, 500]})
+        s = put(f"far_skip_{lay}", objs, lights, recursion=1)
+        s["screen"] = {"dpi": int(detail * dpi * 200), "dimensions": [0.02, 0.015], "position": [-0.01 + 0.000003, -0.0075 - 0.0000015, 0],
+                       "observer": [0, 0, 5]}
+
+    # ---- specular exponents
+    def expo_sphere(k):
+        i, j = k % 5, k // 5
+        ks = 0.4 + 0.5 * ((k * 4) % 15) / 14.0
+        return _sph([-1.6 + 0.8 * i, 1.2 - 0.9 * j, 0.0], 0.38,
+                    _mat([0.3 + 0.1 * (k % 5), 0.25, 0.7 - 0.1 * (k % 4)], specular=[ks, ks, ks],
+                         shininess=SHADING_EXPONENTS[k]))
+    expo_lights = [{"position": [0.6, 1.2, 6.0], "intensity": [30, 30, 30]},
+                   {"position": [-2.5, 3.0, 5.0], "intensity": [20, 25, 30]}]
+    expo_dpi = int(detail * ((dpi * 8) // 3))
+    s = put("exponents_wave", [_floor(-1.5)] + [expo_sphere(k) for k in range(15)], expo_lights, scr_dpi=expo_dpi)
+    s["screen"]["position"] = [-2, -1.2, 0]
+    for i in range(5):   # fewer than 4 bounded objects: one column of three at a time
+        s = put(f"exponents_few{i}", [_floor(-1.5)] + [expo_sphere(i + 5 * j) for j in range(3)], expo_lights,
+                scr_dpi=expo_dpi)
+        s["screen"]["dimensions"] = [0.75, 3]
+        s["screen"]["position"] = [-1.6 + 0.8 * i - 0.375, -1.2, 0]
+
+    # ---- extreme intensities and coefficients
+    for lay in ("few", "csg"):
+        objs = shading_layout(lay)
+        objs[0] = _floor(ambient=[0, 0, 0])
+        objs[1]["sphere"]["color"] = {"diffuse": [1.5, 1.2, 2.0], "ambient": [0, 0, 0], "shininess": 6}   # ks = 0
+        objs[2]["sphere"]["color"] = _mat([0.6, 0.7, 0.2], specular=[0.9, 0.9, 0.9], shininess=3)         # kd -> 0
+        lights = [{"position": [1.0, 1.5, 1.0], "intensity": [60, 50, 40]},
+                  {"position": [-3, 4, 2], "intensity": [-4, 6, -1]},
+                  {"position": [2, 5, -4], "intensity": [5, 5, 5]}]
+        put(f"extremes_{lay}", objs, lights)
+
+    # ---- a medium that is not vacuum
+    tir = _sph([-1.2, -0.3, -1.0], 0.8, _mat([0.2, 0.2, 0.3], refracted=[0.8, 0.8, 0.8]), index=1.0)
+    same = _sph([0.6, -0.5, -0.6], 0.6, _mat([0.3, 0.2, 0.2], refracted=[0.7, 0.7, 0.7]), index=1.33)
+    both = _sph([0.3, 0.9, -2.2], 0.7, _mat([0.2, 0.3, 0.2], refracted=[0.5, 0.5, 0.5], reflected=[0.4, 0.4, 0.4]),
+                index=1.5)
+    glass = _sph([1.7, 0.2, -1.5], 0.5, _mat([0.1, 0.1, 0.1], refracted=[0.9, 0.9, 0.9]), index=1.5)
+    mirror = _sph([-1.6, 1.1, -2.4], 0.5, _mat([0.2, 0.2, 0.2], reflected=[0.8, 0.8, 0.8]))
+    lens = {"difference": [_sph([1.5, -0.7, 0.2], 0.45, _mat([0.2, 0.2, 0.4], refracted=[0.8, 0.8, 0.8]), index=1.5),
+                           _sph([1.5, -0.5, 0.6], 0.3, _mat([0.9, 0.3, 0.3]))]}
+    media = {"few": [_floor(), tir, same, both], "wave": [_floor(), tir, same, both, glass, mirror],
+             "csg": [_floor(), tir, same, both, glass, mirror, lens]}
+    for name, lay, rec in (("media_few", "few", 4), ("media_wave", "wave", 4), ("media_csg", "csg", 4),
+                           ("media_few_rec2", "few", 2), ("media_few_rec1", "few", 1)):
+        put(name, media[lay], None, recursion=rec)["medium"]["index"] = 1.33
+
+    # ---- null materials (shading_patches: the spheres at NULL_CENTRES)
+    n0 = _sph(NULL_CENTRES[0], 0.7, _mat([0.5, 0.5, 0.5]))
+    shiny = _sph([0.9, -0.4, -1.6], 0.8, _mat([0.2, 0.3, 0.4], reflected=[0.7, 0.7, 0.7]))
+    put("null_mat_few", [_floor(), n0, shiny], None)
+    left = {"union": [_sph(NULL_CENTRES[1], 0.5, _mat([0.5, 0.5, 0.5])),
+                      _sph([-0.1, 0.85, -2.0], 0.5, _mat([0.3, 0.8, 0.3]))]}
+    right = {"union": [_sph([1.3, 0.9, -1.2], 0.45, _mat([0.8, 0.8, 0.2])),
+                       _sph(NULL_CENTRES[2], 0.45, _mat([0.5, 0.5, 0.5]))]}
+    glass2 = _sph([0.0, -0.7, 0.2], 0.4, _mat([0.1, 0.1, 0.1], refracted=[0.9, 0.9, 0.9]), index=1.5)
+    poke = {"pokeball": {"position": [-1.7, 1.2, -1.0], "radius": 0.35, "button_dir": [0.2, 0.1, 1.0]}}
+    put("null_mat_csg", [_floor(), n0, shiny, left, right, glass2, poke], None)
+    return sc
+
+
+NULL_CENTRES = ([-1.3, -0.5, -1.0], [-0.6, 0.8, -2.0], [1.8, 0.9, -1.2])
+
+
+def shading_patches(name: str) -> dict:
+    """What shading_scenes()[name] needs beyond its JSON: "null" the centres of
+    the spheres that lose their material (rt_node.mat = -1), "kd0" the centres
+    of the spheres whose material gets kd = 0."""
+    if name == "null_mat_few":
+        return {"null": [NULL_CENTRES[0]], "kd0": []}
+    if name == "null_mat_csg":
+        return {"null": list(NULL_CENTRES), "kd0": []}
+    if name.startswith("extremes_"):
+        return {"null": [], "kd0": [[0.9, -0.4, -1.6]]}
+    return {"null": [], "kd0": []}
+
+
+def shading_patch_indices(rt, sc, name: str) -> tuple[list, list]:
+    """shading_patches(name) as (null node indices, kd = 0 material indices) of the loaded scene."""
+    p = shading_patches(name)
+    null_nodes = rt.sphere_nodes_at(sc, p["null"])
+    kd0 = [int(sc.desc.nodes[i].mat) for i in rt.sphere_nodes_at(sc, p["kd0"])]
+    return null_nodes, kd0
+
+
+def shading_apply(rt, sc, null_nodes, kd0_mats):
+    if len(kd0_mats):
+        sc = rt.with_material_fields(sc, {int(m): {"kd": 0.0} for m in kd0_mats})
+    if len(null_nodes):
+        sc = rt.with_null_materials(sc, null_nodes)
+    return sc
+
+
+def shading_load(rt, name: str, scene: dict):
+    """shading_scenes()[name] as a loaded scene (rt = the rtamd module)."""
+    sc = rt.load_scene_from_json_text(json.dumps(scene))
+    return shading_apply(rt, sc, *shading_patch_indices(rt, sc, name))
+
+
+def shading_light_branches(rt, sc, with_shadows: bool = False) -> list[dict]:
+    """Which branches of the point-light loop (shading.cpp:79-104) the frame's
+    pixel-centre primary hits reach, per light, computed from the oracle's hits
+    alone (rt.oracle_primary_hits): counts of hits that face the light
+    (n . wi > 0) and have
+      clamped   dist_squared <= 0.01
+      half      a clamped distance below 0.5 (effective_dist = 0.5)
+      skipped   max_shadow_t <= shadow_epsilon
+      queried   a shadow query
+      lit       (with_shadows) a shadow query that finds nothing."""
+    import numpy as np
+
+    rec = rt.oracle_primary_hits(sc)
+    h = rec[rec["hit"] & (rec["mat"] >= 0)]
+    eps = np.maximum(1e-3, 1e-4 * h["t"])
+    d = sc.desc
+    out = []
+    for li in range(d.n_lights):
+        tl = np.array(d.lights[li].pos[:]) - h["p"]
+        d2 = (tl * tl).sum(1)
+        clamped = d2 <= 0.01
+        dist = np.sqrt(np.where(clamped, 0.01, d2))
+        wi = tl / dist[:, None]
+        facing = (h["n"] * wi).sum(1) > 0.0
+        skipped = facing & (dist - eps <= eps)
+        queried = facing & ~skipped
+        b = {"clamped": int((facing & clamped).sum()), "half": int((facing & (dist < 0.5)).sum()),
+             "skipped": int(skipped.sum()), "queried": int(queried.sum())}
+        if with_shadows:
+            q = np.flatnonzero(queried)
+            so = h["p"][q] + h["n"][q] * eps[q, None]
+            occ = rt.oracle_occluded(sc, so, wi[q], eps[q], dist[q] - eps[q])
+            b["lit"] = int((~occ).sum())
+        out.append(b)
+    return out
+
+
+def deep_recursion_scene(recursion: int, dpi: int = 8) -> dict:
+    """deep_scenes()["mirrors_rec24"] at another medium.recursion, its opaque
+    sphere given kr and kt > 0 so that both child slots of a frame are used at
+    the deepest level (the stack tiers of rt_launch.hpp: kMaxDepth = 16 frames,
+    kBigDepth = 128)."""
+    s = deep_scenes(dpi=dpi)["mirrors_rec24"]
+    col = s["objects"][2]["sphere"]["color"]
+    col["reflected"] = [0.3, 0.3, 0.3]
+    col["refracted"] = [0.5, 0.5, 0.5]
+    s["objects"][2]["sphere"]["index"] = 1.3
+    s["medium"]["recursion"] = recursion
+    return s

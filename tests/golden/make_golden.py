@@ -23,7 +23,13 @@ turned into IR by our loader (librt_host.so).  Outputs are data only:
   bvh.npz      frames + counts of the wave-BVH scenes (scenes.bvh_scenes:
                a 576-sphere lattice, exact closest-hit ties), both modes
 
-Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh]
+  shading.npz  frames + counts of the shading scene family
+               (scenes.shading_scenes: 33-65 lights, near and skipped lights,
+               specular exponents, extreme coefficients, a non-vacuum medium,
+               null materials), both modes, with each scene's JSON and the
+               nodes / materials patched through the IR
+
+Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh shading]
 """
 from __future__ import annotations
 
@@ -84,9 +90,19 @@ def make_frames():
     print("frames:", len(data))
 
 
+def deep_golden_scenes() -> dict[str, dict]:
+    """scenes.deep_scenes plus the recursion depths at the common kernels'
+    stack edge (kMaxDepth = 16 frames: medium.recursion 17 the last on the
+    common kernels, 18 the first on the big-stack ones)."""
+    out = scenes.deep_scenes(dpi=12)
+    for rec in (17, 18):
+        out[f"mirrors_rec{rec}"] = scenes.deep_recursion_scene(rec, dpi=8)
+    return out
+
+
 def make_deep():
     data = {}
-    for name, d in scenes.deep_scenes(dpi=12).items():
+    for name, d in deep_golden_scenes().items():
         text = json.dumps(d)
         sc = rtamd.load_scene_from_json_text(text)
         for mode in (0, 1):
@@ -238,6 +254,29 @@ def make_bvh():
     print("bvh:", len(data))
 
 
+SHADING_DPI = 12
+
+
+def make_shading():
+    """The shading scene family (scenes.shading_scenes), both modes."""
+    data = {}
+    for name, d in scenes.shading_scenes(dpi=SHADING_DPI, detail=0.5).items():
+        text = json.dumps(d)
+        plain = rtamd.load_scene_from_json_text(text)
+        null_nodes, kd0 = scenes.shading_patch_indices(rtamd, plain, name)
+        sc = scenes.shading_apply(rtamd, plain, null_nodes, kd0)
+        for mode in (0, 1):
+            with quiet_stdout():
+                fb, ni, no = rtamd.ref_render(sc, sc.width, sc.height, mode)
+            data[f"{name}/{mode}/fb"] = fb
+            data[f"{name}/{mode}/counts"] = np.array([ni, no], dtype=np.int64)
+        data[f"{name}/scene"] = np.frombuffer(text.encode(), dtype=np.uint8)
+        data[f"{name}/null_nodes"] = np.array(null_nodes, dtype=np.int32)
+        data[f"{name}/kd0_mats"] = np.array(kd0, dtype=np.int32)
+    np.savez_compressed(os.path.join(HERE, "shading.npz"), **data)
+    print("shading:", len(data))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         for what in sys.argv[1:]:
@@ -251,3 +290,4 @@ if __name__ == "__main__":
     make_deep()
     make_crowd()
     make_bvh()
+    make_shading()

@@ -94,3 +94,51 @@ def test_beyond_big_stacks_refused(gpu):
 def test_fp32_fast_path_refuses_deep_scene(gpu):
     msg = _refused(gpu, json.dumps(scenes.deep_scenes(dpi=4)["csg_right12"]), flags=gpu.RT_FLAG_FP32)
     assert "FP32" in msg
+
+
+# The stack tiers of the recursion (rt_launch.hpp): kMaxDepth = 16 frames, so
+# medium.recursion 17 is the last value on the common kernels and 18 the first
+# on the big-stack ones; kBigDepth = 128 frames, so 129 is the last accepted
+# value and 130 the first refused.  17 and 18 use scenes.deep_recursion_scene
+# (a sphere with kr and kt > 0: both child slots of a frame are used at the
+# deepest level; pinned to the reference in tests/golden/deep.npz).  At 129 the
+# same sphere makes the reference's call tree (two children per hit, tracer.cpp:
+# 38-68) too large for the CPU oracle to finish, so that depth runs the
+# one-child-per-hit mirrors scene.
+def _tier_scene(rec):
+    if rec <= 18:
+        return scenes.deep_recursion_scene(rec, dpi=10)
+    d = scenes.deep_scenes(dpi=10)["mirrors_rec24"]
+    d["medium"]["recursion"] = rec
+    return d
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rec,ns", [(17, "rtd::"), (18, "rtdb::"), (129, "rtdb::")])
+def test_recursion_at_stack_tier_edges(gpu, rec, ns):
+    sc = gpu.load_scene_from_json_text(json.dumps(_tier_scene(rec)))
+    rc, name = gpu.kernel_name(sc, 0)
+    assert rc == 0 and name.startswith(ns), (rc, name)
+    W, H = sc.width, sc.height
+    st = gpu.Stats()
+    fb = gpu.Tracer(sc, W, H, 0).render(st)
+    ref, ost = gpu.oracle_render(sc, W, H, 0, threads=8)
+    d = float(np.abs(fb - ref).max())
+    print(f"  recursion {rec} {W}x{H} {name} max|d|={d:.3g} rays=({st.rays_intersect},{st.rays_occluded})")
+    assert d <= TOL
+    assert (st.rays_intersect, st.rays_occluded) == (ost.rays_intersect, ost.rays_occluded)
+
+
+@pytest.mark.gpu
+def test_recursion_130_refused_for_frames_not_queries(gpu):
+    text = json.dumps(_tier_scene(130))
+    msg = _refused(gpu, text)
+    assert "exceeds the device stacks" in msg and "medium.recursion 130" in msg
+    rc, _ = gpu.kernel_name(gpu.load_scene_from_json_text(text), 0)
+    assert rc == RT_ERR_UNSUPPORTED
+    # queries need no frames: the same scene answers them
+    sc = gpu.load_scene_from_json_text(text)
+    eye = np.array(sc.desc.camera.eye[:])
+    dirs = np.array([[0.0, -0.3, -1.0], [0.0, 0.3, -1.0], [-0.15, -0.05, -1.0]])
+    got = gpu.query_intersect(sc, np.broadcast_to(eye, dirs.shape), dirs)
+    assert got.hit.all() and np.all(got.t > 0)

@@ -273,17 +273,46 @@ def test_oracle_dir_lights_bit_exact(rt, mode):
 @pytest.mark.parametrize("mode", [0, 1])
 def test_oracle_deep_scenes_bit_exact(rt, mode):
     """Scenes beyond the device's common stacks (scenes.deep_scenes:
-    recursion 24, 12 nested transforms, a 12-leaf right-nested csg) against
-    frames of the reference itself (tests/golden/deep.npz, make_golden.py)."""
+    recursion 24, 12 nested transforms, a 12-leaf right-nested csg) and the
+    recursion depths at the stack-tier edge (scenes.deep_recursion_scene:
+    medium.recursion 17 and 18, a sphere with kr and kt) against frames of the
+    reference itself (tests/golden/deep.npz, make_golden.py)."""
     fr = np.load(os.path.join(GOLDEN, "deep.npz"))
     names = _scene_names(fr)
-    assert set(names) == {"mirrors_rec24", "xform_nest12", "csg_right12"}
+    assert set(names) == {"mirrors_rec24", "xform_nest12", "csg_right12", "mirrors_rec17", "mirrors_rec18"}
     for name in names:
         sc = rt.load_scene_from_json_text(bytes(fr[f"{name}/scene"]).decode())
         fb, st = rt.oracle_render(sc, sc.width, sc.height, mode, threads=4)
         assert np.array_equal(fb, fr[f"{name}/{mode}/fb"]), name
         cnt = fr[f"{name}/{mode}/counts"]
         assert (st.rays_intersect, st.rays_occluded) == (int(cnt[0]), int(cnt[1])), name
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_oracle_shading_bit_exact(rt, mode):
+    """The shading scene family (scenes.shading_scenes: more than 32 lights,
+    near and skipped lights, every kind of specular exponent, extreme
+    coefficients, a medium of index 1.33, null materials) against frames of
+    the reference itself (tests/golden/shading.npz, make_golden.py), bit for
+    bit with equal counts; non-finite values (pow(0, -2)) of the same kind in
+    the same place."""
+    import scenes
+
+    fr = np.load(os.path.join(GOLDEN, "shading.npz"))
+    names = _scene_names(fr)
+    assert set(names) == set(scenes.shading_scenes())
+    n_null = 0
+    for name in names:
+        sc = rt.load_scene_from_json_text(bytes(fr[f"{name}/scene"]).decode())
+        null_nodes, kd0 = fr[f"{name}/null_nodes"], fr[f"{name}/kd0_mats"]
+        assert (list(null_nodes), list(kd0)) == tuple(map(list, scenes.shading_patch_indices(rt, sc, name))), name
+        sc = scenes.shading_apply(rt, sc, null_nodes, kd0)
+        n_null += len(null_nodes)
+        fb, st = rt.oracle_render(sc, sc.width, sc.height, mode, threads=4)
+        assert np.array_equal(fb, fr[f"{name}/{mode}/fb"], equal_nan=True), name
+        cnt = fr[f"{name}/{mode}/counts"]
+        assert (st.rays_intersect, st.rays_occluded) == (int(cnt[0]), int(cnt[1])), name
+    assert n_null == 4
 
 
 def test_oracle_cfg5_standard_960_counts_match_reference(rt):
