@@ -62,6 +62,29 @@ int rt_test_kernel_name(const struct rt_scene* s, int mode, int flags, char* out
  * refused here too.  Host only. */
 int rt_test_query_kernel_name(const struct rt_scene* s, int kind, int flags, char* out, int cap);
 
+/* The launch log: which kernels ran.  rt_test_kernel_name above is the plan
+ * for a frame whose wave BVH is on and untimed; the frame itself may drop the
+ * BVH (its trial frames) or launch the timed build of a paper kernel (the
+ * first frame of a scene and shape).  The log records what the launchers of
+ * rt_kernels.hpp / rt_query_kernels.hpp were asked for, host side only.
+ * on != 0: clear the log and start recording; 0: stop.  Process-wide,
+ * thread-safe; while recording is off a launch pays one relaxed atomic load. */
+int rt_test_launch_log(int on);
+/* The kernels launched since recording started, in launch order, one
+ * "ns::name" per line (the table row's own name string; finish kernels as
+ * "ns::k_paper_finish<CODES, PAIR>"; query kernels likewise), NUL-terminated
+ * into out[0..cap).  Returns the number of launches recorded, <0 on error
+ * (RT_ERR_INVALID_ARG: cap too small). */
+int rt_test_launch_log_get(char* out, int cap);
+
+/* Row `index` of launch table `table`: 0 rtd std, 1 rtd paper, 2 rtf std,
+ * 3 rtf paper, 4 rtdb std, 5 rtdb paper, 6 rtd query, 7 rtdb query,
+ * 8 finish kernels (rtd's, then rtf's: big-stack frames finish with rtd's).
+ * Read from the tables the launchers search, so a build's ifdefs are
+ * honoured.  "ns::name" into out; returns RT_OK, or RT_ERR_INVALID_ARG past
+ * the end.  Host only. */
+int rt_test_kernel_row(int table, int index, char* out, int cap);
+
 /* GPU: the shared-denominator division of the device code (rt_device.hpp
  * div3) next to the compiler's own division on the same inputs:
  * div3_host[3i+k] and plain_host[3i+k] = a[3i+k] / b[i].  Tests require the

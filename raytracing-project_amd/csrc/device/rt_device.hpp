@@ -45,6 +45,12 @@ using MatT = rtamd::MatR<real>;
 using LightT = rtamd::LightR<real>;
 using DLightT = rtamd::DLightR<real>;
 using FoldT = rtamd::FoldLeafR<real>;
+// this namespace as the launch log and the test hooks print it ("rtd", "rtf", "rtdb")
+#define RT_STR2(x) #x
+#define RT_STR(x) RT_STR2(x)
+constexpr const char* kNsName = RT_STR(RT_NS);
+#undef RT_STR
+#undef RT_STR2
 #define RV(x) static_cast<real>(x)
 #define RT_INF static_cast<real>(__builtin_inf())
 

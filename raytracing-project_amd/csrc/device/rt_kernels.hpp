@@ -648,11 +648,35 @@ const KernelRow<PaperParams> kPaperKernels[] = {
 #undef RT_STD
 #undef RT_ROW
 
+// The finish kernels by (CODES, PAIR).  RT_NO_PAPER_CODES (the FP32 build)
+// drops the CODES rows: paper codes need an FP64 frame (rt_render.hip
+// frame_trace refuses them with RT_FLAG_FP32, and rt_dist.hip gathers doubles
+// from FP32 ranks), so no frame can ask this namespace for them.
+struct FinishRow {
+    bool codes, pair;
+    void (*fn)(PaperParams);
+    const char* name;
+};
+#define RT_FIN(codes, pair, ...) {codes, pair, __VA_ARGS__, #__VA_ARGS__}
+const FinishRow kFinishKernels[] = {
+    RT_FIN(0, 0, k_paper_finish<false, false>),
+    RT_FIN(0, 1, k_paper_finish<false, true>),
+#ifndef RT_NO_PAPER_CODES
+    RT_FIN(1, 0, k_paper_finish<true, false>),
+    RT_FIN(1, 1, k_paper_finish<true, true>),
+#endif
+};
+#undef RT_FIN
+
 template <class P, size_t N>
 const KernelRow<P>* find_kernel(const KernelRow<P> (&table)[N], unsigned key) {
     for (const KernelRow<P>& r : table)
         if (r.key == key) return &r;
     return nullptr;
+}
+template <class R, size_t N>
+const char* row_name(const R (&table)[N], int i) {
+    return i >= 0 && i < (int)N ? table[i].name : nullptr;
 }
 // (the standard-mode kernels have no timed build, the paper ones no SEC)
 const KernelRow<StdParams>* std_row(const rtamd::KernelVariant& v) {
@@ -671,6 +695,7 @@ hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const Scene
     if (!k) return hipErrorInvalidDeviceFunction;
     const DevScene S = make_scene(V, v.wv == 2);
     const dim3 grid((P.W + kStdBlockX - 1) / kStdBlockX, (P.n_rows + kStdBlockY - 1) / kStdBlockY);
+    rtamd::note_launch(kNsName, k->name);
     hipLaunchKernelGGL(k->fn, grid, dim3(kStdThreads), kStdPool, st, S, P);
     return hipGetLastError();
 }
@@ -680,6 +705,7 @@ hipError_t launch_paper(const rtamd::KernelVariant& v, dim3 grid, hipStream_t st
     const KernelRow<PaperParams>* k = paper_row(v);
     if (!k) return hipErrorInvalidDeviceFunction;
     const DevScene S = make_scene(V, v.wv == 2);
+    rtamd::note_launch(kNsName, k->name);
     hipLaunchKernelGGL(k->fn, pgrid(grid), dim3(kPaperThreads), kPaperPool, st, S, P);
     return hipGetLastError();
 }
@@ -699,19 +725,25 @@ rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v) {
 int kernel_block_threads(bool paper) { return paper ? kPaperThreads : kStdThreads; }
 size_t kernel_pool_bytes(bool paper) { return paper ? kPaperPool : kStdPool; }
 
-void launch_paper_finish(dim3 grid, hipStream_t st, const PaperParams& P) {
+hipError_t launch_paper_finish(dim3 grid, hipStream_t st, const PaperParams& P) {
     // (grid.x covers W pixels one per thread; even W: two per thread; grid.y
     // kFinishRows * kFinishRounds rows per block)
+    const bool codes = P.code != nullptr, pair = P.W % 2 == 0;
+    const FinishRow* k = nullptr;
+    for (const FinishRow& r : kFinishKernels)
+        if (r.codes == codes && r.pair == pair) k = &r;
+    if (!k) return hipErrorInvalidDeviceFunction;
     grid.y = (P.n_rows + kFinishRows * kFinishRounds - 1) / (kFinishRows * kFinishRounds);
-    const dim3 blk(64 * kFinishRows);
-    if (P.W % 2 == 0) {
-        const dim3 g2((P.W / 2 + 63) / 64, grid.y);
-        if (P.code) hipLaunchKernelGGL((k_paper_finish<true, true>), g2, blk, 0, st, P);
-        else hipLaunchKernelGGL((k_paper_finish<false, true>), g2, blk, 0, st, P);
-    } else {
-        if (P.code) hipLaunchKernelGGL((k_paper_finish<true, false>), grid, blk, 0, st, P);
-        else hipLaunchKernelGGL((k_paper_finish<false, false>), grid, blk, 0, st, P);
-    }
+    if (pair) grid.x = (P.W / 2 + 63) / 64;
+    rtamd::note_launch(kNsName, k->name);
+    hipLaunchKernelGGL(k->fn, grid, dim3(64 * kFinishRows), 0, st, P);
+    return hipGetLastError();
 }
+
+// Row i of this namespace's tables as written above (nullptr past the end):
+// what rt_test_kernel_row enumerates.
+const char* std_row_name(int i) { return row_name(kStdKernels, i); }
+const char* paper_row_name(int i) { return row_name(kPaperKernels, i); }
+const char* finish_row_name(int i) { return row_name(kFinishKernels, i); }
 
 }  // namespace RT_NS

@@ -5,6 +5,7 @@
 #define RT_REAL float
 #define RT_NS rtf
 #define RT_NO_PLAIN   // (no plain kernel variants in the FP32 diagnostic build)
+#define RT_NO_PAPER_CODES   // (paper codes are FP64 frames only: no CODES finish kernels)
 #include "rt_device.hpp"
 #include "rt_kernels.hpp"
 
@@ -15,4 +16,5 @@ hipError_t launch_query(const rtamd::KernelVariant&, int, hipStream_t, const rta
     return hipErrorInvalidDeviceFunction;
 }
 rtamd::KernelEntry query_kernel(const rtamd::KernelVariant&, int) { return rtamd::KernelEntry{nullptr, nullptr}; }
+const char* query_row_name(int) { return nullptr; }
 }  // namespace rtf

@@ -167,20 +167,26 @@ struct KernelEntry {
     const char* name;
 };
 
+// The launch log (rt_test.h rt_test_launch_log; defined in rt_test_hooks.hip):
+// every launcher below reports the row it launches, "ns::name".  While the
+// log is off this is one relaxed atomic load.
+void note_launch(const char* ns, const char* name);
+
 }  // namespace rtamd
 
 // The trace kernels of one namespace (rt_kernels.hpp), by KernelVariant
 // (frame_plan.hpp).  launch_*: hipErrorInvalidDeviceFunction when the
 // namespace has no kernel for the variant.  launch_query / query_kernel: the
 // ray-query kernels (rt_query_kernels.hpp, their own translation units; rtf
-// has none).
+// has none).  *_row_name(i): row i of the namespace's table, nullptr past its
+// end (rt_test_kernel_row).
 #define RT_DECLARE_LAUNCHERS(NS)                                                                                  \
     namespace NS {                                                                                                \
     hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,               \
                           const rtamd::StdParams& P);                                                             \
     hipError_t launch_paper(const rtamd::KernelVariant& v, dim3 grid, hipStream_t st, const rtamd::SceneView& V,  \
                             const rtamd::PaperParams& P);                                                         \
-    void launch_paper_finish(dim3 grid, hipStream_t st, const rtamd::PaperParams& P);                             \
+    hipError_t launch_paper_finish(dim3 grid, hipStream_t st, const rtamd::PaperParams& P);                       \
     rtamd::KernelEntry std_kernel(const rtamd::KernelVariant& v);                                                 \
     rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v);                                               \
     int kernel_block_threads(bool paper);                                                                         \
@@ -188,6 +194,10 @@ struct KernelEntry {
     hipError_t launch_query(const rtamd::KernelVariant& v, int kind, hipStream_t st, const rtamd::SceneView& V,   \
                             const rtamd::QueryParams& P);                                                         \
     rtamd::KernelEntry query_kernel(const rtamd::KernelVariant& v, int kind);                                     \
+    const char* std_row_name(int i);                                                                              \
+    const char* paper_row_name(int i);                                                                            \
+    const char* finish_row_name(int i);                                                                           \
+    const char* query_row_name(int i);                                                                            \
     }
 RT_DECLARE_LAUNCHERS(rtd)
 RT_DECLARE_LAUNCHERS(rtf)
@@ -206,9 +216,8 @@ inline hipError_t launch_paper(const KernelVariant& v, dim3 grid, hipStream_t st
                                        : v.ns == KernelVariant::kRtdb ? rtdb::launch_paper(v, grid, st, V, P)
                                                                       : rtd::launch_paper(v, grid, st, V, P);
 }
-inline void launch_paper_finish(const KernelVariant& v, dim3 grid, hipStream_t st, const PaperParams& P) {
-    if (v.ns == KernelVariant::kRtf) rtf::launch_paper_finish(grid, st, P);
-    else rtd::launch_paper_finish(grid, st, P);
+inline hipError_t launch_paper_finish(const KernelVariant& v, dim3 grid, hipStream_t st, const PaperParams& P) {
+    return v.ns == KernelVariant::kRtf ? rtf::launch_paper_finish(grid, st, P) : rtd::launch_paper_finish(grid, st, P);
 }
 // The variant's trace kernel of `mode` ({nullptr, nullptr}: none), and its launch shape
 inline KernelEntry trace_kernel(const KernelVariant& v, bool paper) {

@@ -133,6 +133,7 @@ hipError_t launch_query(const rtamd::KernelVariant& v, int kind, hipStream_t st,
     const size_t waves = (P.n + kQueryThreads - 1) / kQueryThreads;
     if (!P.n || waves > 0x7fffffffu) return hipErrorInvalidValue;
     const DevScene S = make_scene(V);
+    rtamd::note_launch(kNsName, k->name);
     hipLaunchKernelGGL(k->fn, dim3((unsigned)waves), dim3(kQueryThreads), 0, st, S, P);
     return hipGetLastError();
 }
@@ -140,6 +141,12 @@ hipError_t launch_query(const rtamd::KernelVariant& v, int kind, hipStream_t st,
 rtamd::KernelEntry query_kernel(const rtamd::KernelVariant& v, int kind) {
     const QueryRow* k = query_row(v, kind);
     return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
+}
+
+// Row i of the query table as written above (nullptr past the end)
+const char* query_row_name(int i) {
+    constexpr int n = (int)(sizeof(kQueryKernels) / sizeof(kQueryKernels[0]));
+    return i >= 0 && i < n ? kQueryKernels[i].name : nullptr;
 }
 
 }  // namespace RT_NS

@@ -661,8 +661,7 @@ int frame_trace(rt_frame* f, int ri0, int ri1, double* fb, hipStream_t hs, uint8
         HIP_TRY(hipEventRecord(ws.pev[call], st));
         for (int w : c.wait) HIP_TRY(hipStreamWaitEvent(st, ws.pev[w], 0));
         dim3 g2((W + 63) / 64, (n + 3) / 4);
-        rtamd::launch_paper_finish(f->kv, g2, st, P);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(rtamd::launch_paper_finish(f->kv, g2, st, P));
     }
     {
         std::lock_guard<std::mutex> lk(g_setup.mu);

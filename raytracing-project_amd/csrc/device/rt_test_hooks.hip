@@ -1,14 +1,17 @@
 // rt_test_hooks.hip — the rt_test_* hooks of include/rt_test.h that need
 // nothing of a frame's state: the jitter-stream checks, the scene compiler's
 // reports, the kernel a frame would launch (pick_variant + the dispatch
-// tables) and the frame planners of csrc/host/frame_plan.hpp.  (The
+// tables), the tables' rows, the launch log the launchers fill
+// (rtamd::note_launch) and the frame planners of csrc/host/frame_plan.hpp.  (The
 // distributed-frame hooks live with their transport in rt_dist.hip, rt_test_div3
 // with the FP64 kernels.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -38,6 +41,74 @@ int scene_variant(const rt_scene* s, int mode, int flags, rtamd::KernelVariant* 
     }
 }
 }  // namespace
+
+// ------------------------------------------------------------- launch log
+// note_launch is called by every launcher (rt_kernels.hpp, rt_query_kernels.hpp)
+// right before its hipLaunchKernelGGL; off, it is one relaxed load.
+namespace {
+std::atomic<int> g_log_on{0};
+std::mutex g_log_mu;
+std::string g_log;      // "ns::name\n" per launch
+int g_log_n = 0;
+}  // namespace
+
+void rtamd::note_launch(const char* ns, const char* name) {
+    if (!g_log_on.load(std::memory_order_relaxed)) return;
+    std::lock_guard<std::mutex> lk(g_log_mu);
+    if (!g_log_on.load(std::memory_order_relaxed)) return;   // (stopped while we waited)
+    g_log.append(ns).append("::").append(name).push_back('\n');
+    ++g_log_n;
+}
+
+extern "C" int rt_test_launch_log(int on) {
+    std::lock_guard<std::mutex> lk(g_log_mu);
+    if (on) {
+        g_log.clear();
+        g_log_n = 0;
+    }
+    g_log_on.store(on ? 1 : 0, std::memory_order_relaxed);
+    return RT_OK;
+}
+
+extern "C" int rt_test_launch_log_get(char* out, int cap) {
+    if (!out || cap <= 0) return RT_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(g_log_mu);
+    if (g_log.size() + 1 > (size_t)cap) {
+        rtamd::set_last_error("rt_test_launch_log_get: the log needs " + std::to_string(g_log.size() + 1) + " bytes");
+        return RT_ERR_INVALID_ARG;
+    }
+    std::memcpy(out, g_log.c_str(), g_log.size() + 1);
+    return g_log_n;
+}
+
+extern "C" int rt_test_kernel_row(int table, int index, char* out, int cap) {
+    if (!out || cap <= 0 || index < 0) return RT_ERR_INVALID_ARG;
+    const char* ns = nullptr;
+    const char* name = nullptr;
+    switch (table) {
+        case 0: ns = "rtd", name = rtd::std_row_name(index); break;
+        case 1: ns = "rtd", name = rtd::paper_row_name(index); break;
+        case 2: ns = "rtf", name = rtf::std_row_name(index); break;
+        case 3: ns = "rtf", name = rtf::paper_row_name(index); break;
+        case 4: ns = "rtdb", name = rtdb::std_row_name(index); break;
+        case 5: ns = "rtdb", name = rtdb::paper_row_name(index); break;
+        case 6: ns = "rtd", name = rtd::query_row_name(index); break;
+        case 7: ns = "rtdb", name = rtdb::query_row_name(index); break;
+        case 8: {
+            // the namespaces rtamd::launch_paper_finish dispatches to (big-stack
+            // frames finish with rtd's kernels), rtd's rows first
+            int n_rtd = 0;
+            while (rtd::finish_row_name(n_rtd)) ++n_rtd;
+            if (index < n_rtd) ns = "rtd", name = rtd::finish_row_name(index);
+            else ns = "rtf", name = rtf::finish_row_name(index - n_rtd);
+            break;
+        }
+        default: return RT_ERR_INVALID_ARG;
+    }
+    if (!name) return RT_ERR_INVALID_ARG;
+    std::snprintf(out, (size_t)cap, "%s::%s", ns, name);
+    return RT_OK;
+}
 
 extern "C" int rt_test_paper_order(int32_t* list, int n, const uint32_t* cost, int n_cost) {
     if (n < 0 || n % 16 || (n && !list) || n_cost < 0 || (n_cost && !cost)) return RT_ERR_INVALID_ARG;

@@ -462,6 +462,46 @@ def kernel_name(scene: Scene, mode: int, flags: int = RT_FLAG_NONE) -> tuple[int
     return rc, buf.value.decode()
 
 
+KERNEL_TABLES = ("rtd std", "rtd paper", "rtf std", "rtf paper", "rtdb std", "rtdb paper", "rtd query", "rtdb query",
+                 "finish")
+
+
+def kernel_rows(table: int) -> list[str]:
+    """rt_test_kernel_row: the rows ("ns::kernel") of launch table `table`
+    (an index into KERNEL_TABLES), read from the table the launcher searches.
+    Host only."""
+    lib = amd_lib()
+    lib.rt_test_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(160)
+    out = []
+    while lib.rt_test_kernel_row(table, len(out), buf, 160) == RT_OK:
+        out.append(buf.value.decode())
+    return out
+
+
+def launch_log(on: bool) -> None:
+    """rt_test_launch_log: clear the launch log and start recording (True), or stop (False)."""
+    _ok(amd_lib().rt_test_launch_log(1 if on else 0), "rt_test_launch_log")
+
+
+def launch_log_get() -> list[str]:
+    """rt_test_launch_log_get: the kernels ("ns::kernel") launched since
+    launch_log(True), in launch order."""
+    lib = amd_lib()
+    lib.rt_test_launch_log_get.argtypes = [C.c_char_p, C.c_int]
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        n = lib.rt_test_launch_log_get(buf, cap)
+        if n >= 0:
+            lines = buf.value.decode().splitlines()
+            assert len(lines) == n, (len(lines), n)
+            return lines
+        if cap >= 1 << 26:
+            raise RTError(n, last_error())
+        cap *= 16
+
+
 def pow_spec(x, y) -> np.ndarray:
     """rt_test_pow_spec: the device's pow_spec(x[i], y[i]) (rt_device.hpp)."""
     lib = amd_lib()

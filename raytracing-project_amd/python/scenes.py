@@ -17,6 +17,7 @@ import copy
 import json
 import math
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SCENE_DIR = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "tests", "golden", "scenes")
@@ -52,6 +53,19 @@ def with_dpi(scene: dict, dpi: int) -> dict:
     """Same screen, different dpi (used to make small parity cases)."""
     s = copy.deepcopy(scene)
     s["screen"]["dpi"] = dpi
+    return s
+
+
+def with_size(scene: dict, width: int, height: int, dpi: int = 16) -> dict:
+    """Same scene and screen centre, a width x height frame at `dpi` (sizes
+    that are no multiple of a wave's tile, odd widths)."""
+    s = copy.deepcopy(scene)
+    scr = s["screen"]
+    dims = scr.get("dimensions", [1, 1])
+    cx, cy = scr["position"][0] + dims[0] / 2, scr["position"][1] + dims[1] / 2
+    scr["dpi"] = dpi
+    scr["dimensions"] = [width / dpi, height / dpi]
+    scr["position"] = [cx - width / dpi / 2, cy - height / dpi / 2, scr["position"][2]]
     return s
 
 
@@ -127,7 +141,17 @@ def bvh_scenes(dpi: int = 16) -> dict[str, dict]:
             reference's order disagree about which of a pair comes first):
             sphere vs union (the sphere wins), union vs union (the earlier
             wins), sphere vs sphere (the later wins), in both orders and
-            different colours."""
+            different colours;
+      ties_mirror  ties with medium.recursion 3 and every 7th pair's visible
+            spheres reflective: a wave BVH, reflection and CSG objects at once
+            (k_std_secw<C, 2, false>, which neither grid - plain - nor ties -
+            no mirrors - picks);
+      nested / nested_mirror  the lattice of ties / ties_mirror without a
+            tie: the second sphere of each pair has the same centre and a
+            radius 0.05 smaller, so it lies inside the first and no two
+            surfaces coincide.  For the FP32 kernels, which cannot keep the
+            exact FP64 equality of t that decides a tie (a ray that sees the
+            inner sphere's colour has lost the outer one)."""
     def mat(k):
         m = _mat([(k % 7) / 7.0, (k % 5) / 5.0, (k % 3) / 3.0], shininess=8 + 4 * (k % 5))
         if k % 5 == 0:
@@ -164,8 +188,33 @@ def bvh_scenes(dpi: int = 16) -> dict[str, dict]:
         else:              # sphere vs sphere: the later one wins
             pair = [bare([1.0, 0.1, 0.1]), bare([1.0, 1.0, 0.1])]
         ties += pair if (k // 3) % 2 == 0 else pair[::-1]
-    return {"grid": _base(grid, recursion=3, dpi=dpi, lights=lights),
-            "ties": _base(ties, recursion=2, dpi=dpi, lights=lights[:2])}
+    def mirror(o):   # (a pair member: a bare sphere, or a union whose first operand is the visible one)
+        if "union" in o:
+            mirror(o["union"][0])
+        else:
+            o["sphere"]["color"]["reflected"] = [0.4, 0.4, 0.4]
+
+    ties_mirror = copy.deepcopy(ties)
+    for k in range(0, 150, 7):
+        mirror(ties_mirror[1 + 2 * k])
+        mirror(ties_mirror[2 + 2 * k])
+    nested = [copy.deepcopy(ties[0])]
+    for k in range(150):
+        i, j = k % 15, k // 15
+        c = [-3.5 + 0.5 * i, -1.0 + 0.3 * j, -2.5 - 0.5 * j]
+        r = 0.18 + 0.04 * (k % 3)
+        outer = {"sphere": {"position": list(c), "radius": r, "color": _mat([1.0, 0.1 + 0.3 * (k % 3), 0.1])}}
+        inner = {"sphere": {"position": list(c), "radius": r - 0.05, "color": _mat([0.1, 0.1, 1.0])}}
+        nested += [outer, inner] if (k // 3) % 2 == 0 else [inner, outer]
+    nested_mirror = copy.deepcopy(nested)
+    for k in range(0, 150, 7):
+        mirror(nested_mirror[1 + 2 * k])
+        mirror(nested_mirror[2 + 2 * k])
+    return {"nested": _base(nested, recursion=2, dpi=dpi, lights=lights[:2]),
+            "nested_mirror": _base(nested_mirror, recursion=3, dpi=dpi, lights=lights[:2]),
+            "grid": _base(grid, recursion=3, dpi=dpi, lights=lights),
+            "ties": _base(ties, recursion=2, dpi=dpi, lights=lights[:2]),
+            "ties_mirror": _base(ties_mirror, recursion=3, dpi=dpi, lights=lights[:2])}
 
 
 def bvh_perf_scene(n: int = 4096, seed: int = 7, dpi: int = 480) -> dict:
@@ -829,3 +878,149 @@ def deep_recursion_scene(recursion: int, dpi: int = 8) -> dict:
     s["objects"][2]["sphere"]["index"] = 1.3
     s["medium"]["recursion"] = recursion
     return s
+
+
+# ------------------------------------------------------------ kernel recipes
+# rt_flags (include/rt.h)
+_COUNT, _NO_CULL, _FP32, _NO_BVH, _FORCE_BVH = 1, 2, 4, 8, 16
+
+
+class Recipe(NamedTuple):
+    """How to launch one row of a launch table (kernel_recipes)."""
+    row: str              # "ns::kernel<...>", the table row's own name
+    scene_name: str       # key of recipe_scene()
+    mode: int             # 0 standard, 1 paper (query rows: 0)
+    flags: int
+    frame: int            # 0-based frame of one Tracer on a fresh scene handle that must launch the row
+    world: int = 1        # > 1: a distributed frame of that many simulated ranks (the CODES finish kernels)
+    query: int = -1       # 0 / 1: the row is the closest-hit / any-hit query kernel
+
+
+def recipe_scene(name: str) -> tuple[str, list | None]:
+    """(JSON text, directional lights or None) of a recipe's scene: the
+    existing families at 64x48 (deep scenes 48x36), "<scene>@WxH" the same
+    screen centre at another size.  The shading scenes used here need no
+    shading_patches()."""
+    base, _, size = name.partition("@")
+    fam, _, key = base.partition("/")
+    lights = None
+    if fam == "cfg":
+        s = json.loads(config_json(int(key), dpi=16)[0])
+    elif fam == "torture":
+        s = torture_scenes(dpi=16)[key]
+    elif fam == "bvh":
+        s = bvh_perf_scene(300, dpi=16) if key == "perf300" else bvh_scenes(16)[key]
+    elif fam == "deep":
+        s = deep_scenes()[key]
+    elif fam == "dir":
+        text, lights = dir_light_cases()[key]
+        s = json.loads(text)
+    elif fam == "shading":
+        s = shading_scenes(dpi=16)[key]
+    # the scenes of tests/test_gpu_query.py, for the query rows
+    elif fam == "query":
+        if key.startswith("torture/"):
+            s = torture_scenes(dpi=24)[key[8:]]
+        elif key.startswith("config"):
+            s = json.loads(config_json(int(key[6:]), dpi=24)[0])
+        else:
+            return recipe_scene(key)
+    else:
+        raise KeyError(name)
+    if size:
+        w, h = (int(v) for v in size.split("x"))
+        s = with_size(s, w, h)
+    return json.dumps(s), lights
+
+
+def kernel_recipes() -> list[Recipe]:
+    """One Recipe per row of every launch table (rt_test.h rt_test_kernel_row):
+    the smallest scene of the existing families whose frame launches the row.
+    Wave-BVH rows (WV = 2) force the BVH and their WV = 1 twins switch it off,
+    so that no BVH trial frame decides the kernel; the untimed paper kernels
+    are the second frame of a scene handle, the timed ones (T = true) the first.
+    tests/test_kernel_table.py holds this list against the tables,
+    tests/test_gpu_kernel_table.py renders every entry."""
+    C, F, NB, FB = _COUNT, _FP32, _NO_BVH, _FORCE_BVH
+    out = []
+
+    def add(row, scene, mode, flags=0, frame=0, **kw):
+        out.append(Recipe(row, scene, mode, flags, frame, **kw))
+
+    b = lambda v: "true" if v else "false"   # noqa: E731
+
+    # the common kernels in both precisions (rtf: no plain rows)
+    for ns, f in (("rtd", 0), ("rtf", F)):
+        # the wave-BVH lattice: FP64 with exact closest-hit ties, FP32 without
+        # (bvh_scenes: whole spheres of ties change colour when FP32 rounding
+        # breaks a tie, which the silhouette bars of the FP32 path do not cover)
+        lean, secw = ("bvh/nested", "bvh/nested_mirror") if f else ("bvh/ties", "bvh/ties_mirror")
+        # ---- standard mode: k_std<E, D, SEC, C, false>
+        for e, d, sec, scene in ((1, 1, 0, "torture/xform_in_csg"), (1, 1, 1, "shading/lights33_xform"),
+                                 (0, 1, 0, "dir/cfg2_sun_back"), (0, 1, 1, "dir/reflect_refract_sun"),
+                                 (0, 0, 1, "shading/media_few")):
+            for c in (0, 1):
+                add(f"{ns}::k_std<{b(e)}, {b(d)}, {b(sec)}, {b(c)}, false>", scene, 0, f | (C if c else 0))
+        # k_std_lean<C, WV, PL>, k_std_secw<C, WV, PL>
+        for c in (0, 1):
+            fc = f | (C if c else 0)
+            add(f"{ns}::k_std_lean<{b(c)}, 0, false>", "cfg/2" if (c or f) else "torture/csg_groups", 0, fc)
+            add(f"{ns}::k_std_lean<{b(c)}, 1, false>", lean, 0, fc | NB)
+            add(f"{ns}::k_std_lean<{b(c)}, 2, false>", lean, 0, fc | FB)
+            add(f"{ns}::k_std_secw<{b(c)}, 1, false>", secw, 0, fc | NB)
+            add(f"{ns}::k_std_secw<{b(c)}, 2, false>", secw, 0, fc | FB)
+        # ---- paper mode: k_paper_primary<E, D, C[, T]>: untimed on the second frame, timed on the first
+        for e, d, scene in ((1, 1, "torture/xform_in_csg"), (0, 1, "dir/cfg2_sun_back")):
+            add(f"{ns}::k_paper_primary<{b(e)}, {b(d)}, false>", scene, 1, f, 1)
+            add(f"{ns}::k_paper_primary<{b(e)}, {b(d)}, false, true>", scene, 1, f, 0)
+            add(f"{ns}::k_paper_primary<{b(e)}, {b(d)}, true>", scene, 1, f | C, 0)
+        # k_paper_primary_lean<C, WV, T, PL>
+        for wv, scene, fl in ((0, "cfg/2" if f else "torture/csg_groups", 0), (1, lean, NB), (2, lean, FB)):
+            add(f"{ns}::k_paper_primary_lean<false, {wv}, false, false>", scene, 1, f | fl, 1)
+            add(f"{ns}::k_paper_primary_lean<false, {wv}, true, false>", scene, 1, f | fl, 0)
+            add(f"{ns}::k_paper_primary_lean<true, {wv}, false, false>", "cfg/2" if wv == 0 else scene, 1, f | fl | C, 0)
+    # ---- the plain kernels (FP64 only, never counting)
+    for wv, scene, fl in ((0, "cfg/2", 0), (1, "bvh/perf300", NB), (2, "bvh/perf300", FB)):
+        add(f"rtd::k_std_lean<false, {wv}, true>", scene, 0, fl)
+        add(f"rtd::k_paper_primary_lean<false, {wv}, false, true>", scene, 1, fl, 1)
+        add(f"rtd::k_paper_primary_lean<false, {wv}, true, true>", scene, 1, fl, 0)
+    add("rtd::k_std_secw<false, 1, true>", "bvh/grid", 0, NB)
+    add("rtd::k_std_secw<false, 2, true>", "bvh/grid", 0, FB)
+    # ---- the big-stack build: general rows only
+    for sec, scene in ((0, "deep/xform_nest12"), (1, "deep/mirrors_rec24")):
+        for c in (0, 1):
+            add(f"rtdb::k_std<true, true, {b(sec)}, {b(c)}, false>", scene, 0, C if c else 0)
+    add("rtdb::k_paper_primary<true, true, false>", "deep/xform_nest12", 1, 0, 1)
+    add("rtdb::k_paper_primary<true, true, false, true>", "deep/xform_nest12", 1, 0, 0)
+    add("rtdb::k_paper_primary<true, true, true>", "deep/xform_nest12", 1, C, 0)
+    # ---- ray queries: k_query_isect / k_query_occl<E, D, PL>
+    for ns, e, d, pl, scene in (("rtd", 1, 1, 0, "query/torture/xform_in_csg"), ("rtd", 0, 1, 0, "query/dir/pokeball_csg_sun"),
+                                ("rtd", 0, 0, 0, "query/bvh/ties"), ("rtd", 0, 0, 1, "query/config3"),
+                                ("rtdb", 1, 1, 0, "query/deep/xform_nest12")):
+        for kind, k in enumerate(("k_query_isect", "k_query_occl")):
+            add(f"{ns}::{k}<{b(e)}, {b(d)}, {b(pl)}>", scene, 0, 0, 0, query=kind)
+    # ---- the finish pass: k_paper_finish<CODES, PAIR>.  PAIR by the width's
+    # parity; CODES in the ranks of a distributed FP64 frame (taller than one
+    # RT_PAPER_STRIP_ROWS strip, so that both ranks render)
+    add("rtd::k_paper_finish<false, false>", "cfg/5@51x36", 1)
+    add("rtd::k_paper_finish<false, true>", "cfg/5@52x36", 1)
+    add("rtd::k_paper_finish<true, false>", "cfg/5@17x48", 1, world=2)
+    add("rtd::k_paper_finish<true, true>", "cfg/5@16x48", 1, world=2)
+    add("rtf::k_paper_finish<false, false>", "cfg/5@51x36", 1, F)
+    add("rtf::k_paper_finish<false, true>", "cfg/5@52x36", 1, F)
+    return out
+
+
+def row_timed(row: str, timed: bool) -> str:
+    """A paper primary row's name with its T argument set (k_paper_primary<E,
+    D, C[, T]>: the untimed rows leave T out; k_paper_primary_lean<C, WV, T,
+    PL>); every other row unchanged."""
+    head, _, args = row.partition("<")
+    a = [v.strip() for v in args.rstrip(">").split(",")]
+    if head.endswith("::k_paper_primary"):
+        a = a[:3] + (["true"] if timed else [])
+    elif head.endswith("::k_paper_primary_lean"):
+        a[2] = "true" if timed else "false"
+    else:
+        return row
+    return f"{head}<{', '.join(a)}>"

@@ -6,7 +6,10 @@ same algorithm (ray counts within a small fraction of the FP64 path's), an
 image that matches the CPU oracle closely everywhere but on a thin set of
 silhouette / CSG-seam / shadow-edge pixels, and the same output contract
 (shape, paper-mode value set).  The FP64 path stays the parity path
-(tests/test_gpu_parity.py)."""
+(tests/test_gpu_parity.py).  These scenes reach only a few of the FP32
+kernels; tests/test_gpu_kernel_table.py renders every row of the rtf launch
+tables (wave BVH, reflection, op counting, timed and untimed paper builds) at
+the bars defined here."""
 import numpy as np
 import pytest
 
