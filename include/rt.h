@@ -198,7 +198,9 @@ typedef struct rt_stats {
     uint64_t rays_occluded;    /* Scene::occluded calls (scene.cpp:33)                         */
     uint64_t rays_traced;      /* intersect+occluded queries actually evaluated on device      */
     uint64_t pixels;
-    double ms_rng;             /* jitter-stream generation (device)                             */
+    double ms_rng;             /* jitter-stream generation (device); ~0 for a standard frame
+                                  whose draws are resident from an earlier frame of the same
+                                  size and rows (RT_JITTER_CACHE_MB): nothing is generated    */
     double ms_kernel;          /* trace kernels (device)                                        */
     double ms_total;           /* whole call, host wall clock                                   */
     uint64_t ops[16];          /* per-op counters when RT_FLAG_COUNT_OPS is set (rt_op_counter) */
@@ -474,7 +476,7 @@ int rt_setup_times(double* out, int n);
 enum { RT_WARM_HOST = 1, RT_WARM_DEVICE = 2 };
 int rt_warmup(int what);
 /* Release every device resource the library caches (per-device workspaces,
- * resident scenes and jitter tables, the rt_render_multi device groups with
+ * resident scenes, jitter tables and jitter draws, the rt_render_multi device groups with
  * their RCCL communicators).  No render may be in flight; later calls
  * re-create what they need.  The `ray` CLI calls it before exit when it
  * rendered on several GPUs (RCCL communicators); a one-GPU run leaves the

@@ -225,6 +225,27 @@ int rt_test_plan_paper_calls(int W, int H, const int32_t* rows, int n_rows, cons
  * indices, -1 padding), given the measured cost of the 8-entry group whose
  * first entry is e in cost[e] (0 = unmeasured).  Returns 0. */
 int rt_test_paper_order(int32_t* list, int n, const uint32_t* cost, int n_cost);
+/* The jitter cache of a workspace (csrc/host/jitter_cache.hpp: a standard
+ * frame's draws stay resident by (W, H, rows)).  rt_test_jitter_cache_stats: of
+ * the calling thread's workspace on the current device; _slot: of workspace
+ * slot `slot` there (0 the process's own, r + 1 simulated rank r's, which
+ * rt_test_dist_threads empties when it returns: entries and bytes are then
+ * 0, the counts stay).  hits = standard frames that ran no jitter fill,
+ * misses = those that ran it (cached or not), entries / bytes = the cached
+ * buffers now (the uncached buffer is not counted).  The counts run from
+ * process start or the last rt_test_jitter_cache_budget; rt_shutdown frees
+ * the entries and keeps the counts.  Both take the workspace lock: not for a
+ * thread between its rt_frame_begin and rt_frame_end. */
+int rt_test_jitter_cache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries, uint64_t* bytes);
+int rt_test_jitter_cache_stats_slot(int slot, uint64_t* hits, uint64_t* misses, uint64_t* entries, uint64_t* bytes);
+/* Set the cache budget of every workspace to `bytes` (0: off; < 0: back to
+ * RT_JITTER_CACHE_MB), free every cached entry and zero the counts, so that
+ * one process can compare cache off, a miss and a hit.  Waits for open frames. */
+int rt_test_jitter_cache_budget(int64_t bytes);
+/* CPU: the cache's key / LRU / budget logic over host memory, driven by a
+ * script (jitter_cache.hpp jitter_cache_sim: ops[5 * n_ops] in, out[8 * n_ops]).
+ * Returns what it returns, or RT_ERR_INVALID_ARG. */
+int rt_test_jitter_cache_sim(const int64_t* ops, int n_ops, int64_t budget, int64_t* out);
 /* GPU: one simulated rank (rank of world) of a distributed frame on the
  * current device through the product's rank path, the RCCL gather replaced by
  * a device copy (rank 0 also places every slot).  Ranks are cached, so a

@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "jitter_cache.hpp"
 #include "mt_jump.hpp"
 #include "pinned.hpp"
 #include "mt_poly.hpp"
@@ -38,6 +39,7 @@
 #include "rt_devbuf.hpp"
 #include "rt_launch.hpp"
 #include "rt_internal.hpp"
+#include "rt_test.h"
 #include "scene_compile.hpp"
 
 using rtamd::kCounterSlots;
@@ -144,6 +146,21 @@ bool bvh_ab() {
     return on;
 }
 
+// Device memory of the jitter cache's buffers (jitter_cache.hpp), on the
+// current device.  A failed allocation is the cache's to handle (it frees
+// entries or takes the uncached buffer), so the runtime's last-error slot is
+// cleared: a later launch check must not report it.
+void* jitter_alloc(size_t bytes) {
+    void* p = nullptr;
+    rtamd::SetupTimer tm(rtamd::kSetupAlloc);
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return p;
+}
+void jitter_free(void* p) { (void)hipFree(p); }
+
 // Per-device workspace (one render at a time per device; guarded by a mutex).
 struct Workspace {
     std::mutex mu;
@@ -151,7 +168,10 @@ struct Workspace {
     DBuf wobjs, wctab, worig, wchunk;   // wave BVH (CompiledScene::wobjs ...)
     DBuf fold;
     DBuf nodes_f, mats_f, lights_f, dlights_f, fold_f;   // float copies (RT_FLAG_FP32)
-    DBuf rows, jit, ckpt, jscratch, counters;
+    // standard mode: the frames' jitter draws and rows lists, resident by
+    // (W, H, rows) so that only the first frame of a key generates them
+    rtamd::JitterCache jcache{jitter_alloc, jitter_free};
+    DBuf ckpt, jscratch, counters;
     DBuf paper_i, paper_d, paper_aux, fb;
     DBuf q_rays, q_hits, q_mask;              // ray queries from host memory: one chunk's rays / hits / flags
     rtamd::JitterTable jtab;                  // mt19937(12345) checkpoint table (resident)
@@ -165,7 +185,6 @@ struct Workspace {
     // mode, flags, rows): the next frame of that key launches its groups
     // costliest first (frame_plan.hpp order_paper_groups)
     std::map<uint64_t, std::vector<uint32_t>> paper_cost;
-    std::vector<int32_t> rows_cached;   // what `rows` holds (a frame with the same rows skips the upload)
     bool counters_zero = false;         // the last frame's k_reduce_counters left `counters` zero (no memset)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> tev;   // one per rt_frame_trace call of the open frame (pool)
@@ -235,6 +254,9 @@ struct rt_frame {
     int bvh_trial = -1;                        // SceneCache::bvh_trial this frame measures (-1: none)
     std::chrono::steady_clock::time_point t_start;
     rtamd::StdPlan std_plan;                   // standard mode (host source of the rows upload)
+    rtamd::JitterCache::Entry* jent = nullptr; //   its buffer in ws->jcache (valid once this frame has ended well)
+    const double* jit = nullptr;               //   the draws, 16 per pixel by jitter row
+    const int32_t* rows = nullptr;             //   rows | jitter row of each, on the device
     rtamd::PaperPlan paper;                    // paper mode (host source of the aux upload)
     rtamd::PaperCalls paper_calls;             //   its trace calls' lists (host sources of their uploads)
     std::vector<hipStream_t> call_st;          // stream of each trace call (ws.tev[i] its end)
@@ -519,21 +541,31 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
     HIP_TRY(hipEventRecord(ws.ev[0], st));
     if (n_rows > 0 && mode == RT_MODE_STANDARD) {
         const rtamd::StdPlan& sp = f->std_plan;
-        HIP_TRY(ws.jit.ensure((size_t)n_rows * 16 * W * sizeof(double)));
-        HIP_TRY(ws.jscratch.ensure(rtamd::mt_fill_scratch_bytes(sp.jranges)));
-        // (the rows / jitter-row lists of the previous frame of this
-        // workspace are still on the device: the same row set skips the copy)
-        if (!(ws.rows.p && ws.rows_cached == sp.rows_jrow)) {
-            HIP_TRY(upload(ws.rows, sp.rows_jrow, st, &ws.up));
-            ws.rows_cached = sp.rows_jrow;
+        // the draws and the rows / jitter-row lists are a function of (W, H,
+        // rows) alone: a frame whose key is resident in the workspace (its
+        // filling frame ended successfully, so the draws are complete
+        // whatever stream this frame runs on) uploads and generates nothing
+        const rtamd::JitterCache::Got got = ws.jcache.acquire(W, H, sp.rows_jrow, (size_t)n_rows * 16 * W * sizeof(double),
+                                                              rtamd::jitter_cache_budget());
+        if (!got.e) {
+            rtamd::set_last_error("rt_render: out of device memory for the frame's jitter draws");
+            return RT_ERR_HIP;
         }
-        ws.jjob.up = &ws.up;
-        const auto t_l = SClock::now();
-        HIP_TRY(rtamd::mt_launch_fill(ws.jtab, sp.jranges, ws.jjob, ws.jscratch.p, ws.jit.as<double>(), st));
-        {
-            std::lock_guard<std::mutex> lk(g_setup.mu);
-            if (!g_setup.jitter_launched) g_setup.jitter_launch_ms = ms_since(t_l);
-            g_setup.jitter_launched = true;
+        f->jent = got.e;
+        f->jit = got.e->jit();
+        f->rows = got.e->rows();
+        if (got.upload_rows)
+            HIP_TRY(rtamd::upload_async(&ws.up, got.e->rows(), sp.rows_jrow.data(), sp.rows_jrow.size() * sizeof(int32_t), st));
+        if (got.fill) {
+            HIP_TRY(ws.jscratch.ensure(rtamd::mt_fill_scratch_bytes(sp.jranges)));
+            ws.jjob.up = &ws.up;
+            const auto t_l = SClock::now();
+            HIP_TRY(rtamd::mt_launch_fill(ws.jtab, sp.jranges, ws.jjob, ws.jscratch.p, got.e->jit(), st));
+            {
+                std::lock_guard<std::mutex> lk(g_setup.mu);
+                if (!g_setup.jitter_launched) g_setup.jitter_launch_ms = ms_since(t_l);
+                g_setup.jitter_launched = true;
+            }
         }
     } else if (n_rows > 0) {
         f->paper = rtamd::plan_paper_frame(rtamd::scene_uid(s), W, H, mode, flags, rows_host, n_rows);
@@ -595,9 +627,9 @@ int frame_trace(rt_frame* f, int ri0, int ri1, double* fb, hipStream_t hs, uint8
         P.W = W;
         P.H = f->H;
         P.n_rows = n;
-        P.rows = ws.rows.as<int32_t>() + ri0;
-        P.jrow = ws.rows.as<int32_t>() + f->n_rows + ri0;
-        P.jit = ws.jit.as<double>();
+        P.rows = f->rows + ri0;
+        P.jrow = f->rows + f->n_rows + ri0;
+        P.jit = f->jit;
         P.fb = fb;
         P.counters = ctr;
         HIP_TRY(rtamd::launch_std(f->kv, st, f->S, P));
@@ -730,6 +762,10 @@ int frame_end_body(rt_frame* f, rt_stats* stats) {
     HIP_TRY(hipEventRecord(ws.ev[3], st));
     HIP_TRY(rtamd::spin_wait(ws.ev[3]));
     ws.counters_zero = true;
+    // every stream of the frame has run to its end: the draws and the rows
+    // list this frame wrote are complete, and later frames of its key may
+    // read them (a frame that fails before this point leaves no valid entry)
+    ws.jcache.complete(f->jent);
     unsigned long long hc[kCounterWords];
     for (int k = 0; k < kCounterWords; ++k) hc[k] = ((volatile unsigned long long*)ws.ctr_host)[k];
     if (timed) {
@@ -997,12 +1033,12 @@ int rtamd::release_device_workspaces(int min_slot) {
         for (DBuf* b : {&w->nodes, &w->mats, &w->lights, &w->dlights, &w->objs, &w->ops, &w->gb, &w->ctab, &w->lrec,
                         &w->lwrec, &w->lgb, &w->fold,
                         &w->wobjs, &w->wctab, &w->worig, &w->wchunk,
-                        &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->rows, &w->jit, &w->ckpt,
+                        &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->ckpt,
                         &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime,
                         &w->q_rays, &w->q_hits, &w->q_mask})
             b->release();
         w->jtab.release();
-        w->rows_cached.clear();
+        w->jcache.release();   // every cached entry and the uncached buffer (the hit / miss counts stay)
         w->counters_zero = false;
         w->up.release();
         if (w->ctr_host) (void)hipHostFree(w->ctr_host);
@@ -1022,6 +1058,51 @@ int rtamd::release_device_workspaces(int min_slot) {
         if (w->aux_st) (void)hipStreamDestroy(w->aux_st);
         w->aux_st = nullptr;
         w->sc = SceneCache();
+    }
+    (void)hipSetDevice(prev);
+    return RT_OK;
+}
+
+// ------------------------------------------------- test hooks (rt_test.h)
+// The jitter cache of workspace (current device, slot).  Takes the workspace
+// lock: not for a thread that holds an open frame of that workspace.
+extern "C" int rt_test_jitter_cache_stats_slot(int slot, uint64_t* hits, uint64_t* misses, uint64_t* entries,
+                                               uint64_t* bytes) {
+    if (!hits || !misses || !entries || !bytes) return RT_ERR_INVALID_ARG;
+    *hits = *misses = *entries = *bytes = 0;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    Workspace* w = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_ws_mu);
+        const auto it = g_ws.find({dev, slot});
+        if (it != g_ws.end()) w = it->second;
+    }
+    if (!w) return RT_OK;   // (no frame of that slot yet)
+    std::lock_guard<std::mutex> wl(w->mu);
+    *hits = w->jcache.hits();
+    *misses = w->jcache.misses();
+    *entries = w->jcache.entries();
+    *bytes = w->jcache.bytes();
+    return RT_OK;
+}
+
+extern "C" int rt_test_jitter_cache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries, uint64_t* bytes) {
+    return rt_test_jitter_cache_stats_slot(t_ws_slot, hits, misses, entries, bytes);
+}
+
+extern "C" int rt_test_jitter_cache_budget(int64_t bytes) {
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    rtamd::set_jitter_cache_budget(bytes);
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    for (auto& kv : g_ws) {
+        Workspace* w = kv.second;
+        if (!w) continue;
+        std::lock_guard<std::mutex> wl(w->mu);   // waits for an open frame of this workspace
+        (void)hipSetDevice(kv.first.first);
+        w->jcache.clear();
+        w->jcache.reset_counts();
     }
     (void)hipSetDevice(prev);
     return RT_OK;

@@ -2,9 +2,11 @@
 // nothing of a frame's state: the jitter-stream checks, the scene compiler's
 // reports, the kernel a frame would launch (pick_variant + the dispatch
 // tables), the tables' rows, the launch log the launchers fill
-// (rtamd::note_launch) and the frame planners of csrc/host/frame_plan.hpp.  (The
+// (rtamd::note_launch), the frame planners of csrc/host/frame_plan.hpp and the
+// jitter cache's logic over host memory (csrc/host/jitter_cache.hpp).  (The
 // distributed-frame hooks live with their transport in rt_dist.hip, rt_test_div3
-// with the FP64 kernels.)
+// with the FP64 kernels, the jitter cache's counts and budget with the
+// workspaces in rt_render.hip.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "frame_plan.hpp"
+#include "jitter_cache.hpp"
 #include "mt_jump.hpp"
 #include "mt_poly.hpp"
 #include "rt.h"
@@ -320,6 +323,20 @@ extern "C" int rt_test_plan_dist(int H, int world, int rank, int mode, int kind,
     }
     if (rowtab_out) std::copy(p.rowtab.begin(), p.rowtab.end(), rowtab_out);
     return RT_OK;
+}
+
+// ------------------------------------------------------ jitter cache (CPU)
+extern "C" int rt_test_jitter_cache_sim(const int64_t* ops, int n_ops, int64_t budget, int64_t* out) {
+    if (n_ops < 0 || (n_ops && (!ops || !out)) || budget < 0) return RT_ERR_INVALID_ARG;
+    for (int k = 0; k < n_ops; ++k) {
+        const int64_t* o = ops + 5 * (size_t)k;
+        if (o[0] < 0 || o[0] > 5) return RT_ERR_INVALID_ARG;
+        if (o[0] <= 1 && (o[1] <= 0 || o[1] > 4096 || o[2] < 0 || o[3] <= 0 || o[3] > 4096 || o[2] + o[3] > (1 << 20) ||
+                          o[4] < 0 || o[4] > (1 << 20)))
+            return RT_ERR_INVALID_ARG;
+        if (o[0] >= 3 && o[0] <= 4 && o[4] < 0) return RT_ERR_INVALID_ARG;
+    }
+    return rtamd::jitter_cache_sim(ops, n_ops, budget, out);
 }
 
 namespace {

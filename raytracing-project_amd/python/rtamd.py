@@ -515,6 +515,48 @@ def pow_spec(x, y) -> np.ndarray:
     return out
 
 
+_u64p = C.POINTER(C.c_uint64)
+
+
+def jitter_cache_stats(slot: int | None = None) -> dict:
+    """rt_test_jitter_cache_stats: {hits, misses, entries, bytes} of the jitter
+    cache of the calling thread's workspace on the current device, or of
+    workspace slot `slot` (r + 1: simulated rank r of dist_threads)."""
+    lib = amd_lib()
+    lib.rt_test_jitter_cache_stats.argtypes = [_u64p] * 4
+    lib.rt_test_jitter_cache_stats_slot.argtypes = [C.c_int] + [_u64p] * 4
+    v = [C.c_uint64() for _ in range(4)]
+    refs = [C.byref(x) for x in v]
+    if slot is None:
+        _ok(lib.rt_test_jitter_cache_stats(*refs), "rt_test_jitter_cache_stats")
+    else:
+        _ok(lib.rt_test_jitter_cache_stats_slot(slot, *refs), "rt_test_jitter_cache_stats_slot")
+    return dict(zip(("hits", "misses", "entries", "bytes"), (int(x.value) for x in v)))
+
+
+def jitter_cache_budget(nbytes: int) -> None:
+    """rt_test_jitter_cache_budget: the cache budget of every workspace in
+    bytes (0: off, < 0: back to RT_JITTER_CACHE_MB); frees every cached entry
+    and zeroes the counts."""
+    lib = amd_lib()
+    lib.rt_test_jitter_cache_budget.argtypes = [C.c_int64]
+    _ok(lib.rt_test_jitter_cache_budget(nbytes), "rt_test_jitter_cache_budget")
+
+
+def jitter_cache_sim(ops, budget: int) -> tuple[int, list[dict]]:
+    """rt_test_jitter_cache_sim: the cache's logic over host memory.  ops:
+    [(op, W, row0, n_rows, arg), ...] (jitter_cache.hpp jitter_cache_sim);
+    returns (status, the state after each op).  Host only."""
+    lib = amd_lib()
+    lib.rt_test_jitter_cache_sim.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.POINTER(C.c_int64)]
+    n = len(ops)
+    flat = (C.c_int64 * (5 * n))(*[int(v) for o in ops for v in o])
+    out = (C.c_int64 * (8 * n))()
+    rc = lib.rt_test_jitter_cache_sim(flat, n, budget, out)
+    names = ("buffer", "fill", "upload_rows", "entries", "bytes", "live", "hits", "misses")
+    return rc, [dict(zip(names, out[8 * k:8 * k + 8])) for k in range(n)]
+
+
 def device_count() -> int:
     return int(amd_lib().rt_device_count())
 

@@ -8,8 +8,9 @@
 // the example, torture and deep scenes plus malformed JSON.  Per scene: load,
 // compile the device object table, pick the frame's kernel variant, render a
 // band of rows on the oracle in both modes, toByte, PNG; then the frame
-// planners over the shapes of tests/test_frame_plan.py.  Exit 0 = no
-// sanitizer report.
+// planners over the shapes of tests/test_frame_plan.py and the jitter cache's
+// logic (jitter_cache.cpp) over the scripts of tests/test_jitter_cache.py.
+// Exit 0 = no sanitizer report.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "frame_plan.hpp"
+#include "jitter_cache.hpp"
 #include "oracle.h"
 #include "rt.h"
 #include "scene_compile.hpp"
@@ -111,6 +113,45 @@ static size_t check_plans() {
     return sum;
 }
 
+// The jitter cache's logic over host memory (jitter_cache.hpp
+// jitter_cache_sim), at the scripts of tests/test_jitter_cache.py: hits,
+// same-size keys, an abandoned frame, evictions, the uncached buffer and
+// allocation failures, so that every buffer the cache hands out, frees or
+// keeps is exercised under the sanitizers.  Returns the number of scripts
+// that reported a stale buffer, a leak or a double free.
+static int check_jitter_cache() {
+    const int64_t e3 = (int64_t)rtamd::JitterCache::entry_bytes(3 * 16 * 2 * sizeof(double), 6);
+    const int64_t big = 1 << 20;
+    struct Script {
+        int64_t budget;
+        std::vector<std::vector<int64_t>> ops;   // {op, W, row0, n_rows, arg}
+    };
+    const std::vector<int64_t> A = {0, 2, 0, 3, 0}, B = {0, 2, 3, 3, 0}, C = {0, 2, 6, 3, 0}, A_left = {1, 2, 0, 3, 0},
+                               wide = {0, 3, 0, 2, 0}, tall = {0, 2, 0, 4, 0}, small = {0, 2, 0, 2, 0};
+    const auto fail = [](int64_t n) { return std::vector<int64_t>{3, 0, 0, 0, n}; };
+    const std::vector<Script> scripts = {
+        {big, {A, A, wide, B, A, wide, B, {0, 2, 0, 3, 56}, A}},   // (arg of a frame: its height, part of the key)
+        {big, {A_left, A, A, A_left, A}},
+        {2 * e3, {A, B, A, C, A, B}},
+        {e3, {A, small, A, small, small, tall, A}},
+        {0, {A, A, B, A}},
+        {e3 - 1, {A, A, B, A, {5, 0, 0, 0, 0}, A}},
+        {big, {A, B, {4, 0, 0, 0, e3}, A, C, C, {2, 0, 0, 0, 0}, A}},
+        {big, {A, fail(1), B, B, A}},
+        {e3, {A, fail(1), tall}},
+        {big, {A, fail(3), B, B}},
+    };
+    int bad = 0;
+    for (const Script& s : scripts) {
+        std::vector<int64_t> ops, out(8 * (s.ops.size() + 1));
+        for (const auto& o : s.ops) ops.insert(ops.end(), o.begin(), o.end());
+        const int64_t release[5] = {5, 0, 0, 0, 0};
+        ops.insert(ops.end(), release, release + 5);
+        bad += rtamd::jitter_cache_sim(ops.data(), (int)s.ops.size() + 1, s.budget, out.data()) != 0;
+    }
+    return bad;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: host_check <out.png> <scene.json>...\n");
@@ -126,5 +167,7 @@ int main(int argc, char** argv) {
         if (rt_scene_load_json_text(t, std::strlen(t), &s) == RT_OK) rt_scene_destroy(s);
     }
     std::printf("plans %zu\n", check_plans());
-    return bad ? 1 : 0;
+    const int bad_cache = check_jitter_cache();
+    std::printf("jitter cache: %d bad scripts\n", bad_cache);
+    return bad || bad_cache ? 1 : 0;
 }
