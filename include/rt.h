@@ -27,6 +27,8 @@
  *                               raytracer/src/scene.cpp:10-24
  *   rt_query_occluded        <- Scene::occluded, a batch of rays
  *                               raytracer/src/scene.cpp:33-42
+ *   rt_query_radiance        <- Tracer::trace, a batch of rays
+ *                               raytracer/src/tracer.cpp:12-73
  *   rt_framebuffer_to_rgb8   <- framebuffer_to_mat_bgr8 / toByte
  *                               raytracer/src/main.cpp:19-34, core.h:313-316
  *   rt_write_png             <- cv::imwrite (main.cpp:86-89)
@@ -61,7 +63,8 @@ extern "C" {
                                  carries the scene hash and the root strip shed
                               (still 6: the batched ray queries rt_query_intersect /
                                rt_query_occluded and their *_device forms, rt_ray and
-                               rt_hit, are pure additions) */
+                               rt_hit, are pure additions, as are the radiance queries
+                               rt_query_radiance / rt_query_radiance_device) */
 
 /* ---------------------------------------------------------------- errors */
 enum rt_status {
@@ -423,6 +426,38 @@ int rt_query_occluded(const rt_scene* s, const rt_ray* rays_host, size_t n, int 
 int rt_query_intersect_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, rt_hit* hits_dev,
                               uint8_t* hit_mask_dev, void* hip_stream, rt_stats* stats);
 int rt_query_occluded_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, uint8_t* occluded_dev,
+                             void* hip_stream, rt_stats* stats);
+
+/* -------------------------------------------------- radiance queries
+ * Tracer::trace(const Ray&) (tracer.cpp:12-73) for a batch of caller-given
+ * rays: the radiance along each ray - closest hit, Phong shading with a shadow
+ * ray to every light (directional lights first), reflection and refraction
+ * recursion - in standard-mode semantics: a miss returns the background,
+ * recursion_limit <= 0 black, a hit on a null material the direct term only.
+ * This is the seam for light baking, irradiance probes, reflection captures,
+ * adaptive resampling and camera models other than the scene's flat screen:
+ * the scene's camera plays no part, and there is no jitter or averaging.
+ *
+ * rgb_host[3i .. 3i+2] = Tracer::trace(Ray(rays_host[i].o, rays_host[i].d)).
+ * The ray is Ray(o, d) as for the other queries (d normalised as in
+ * core.h:278, a direction of length <= 1e-6 becomes (0, 1, 0)); tmin and tmax
+ * of rt_ray are NOT READ: Tracer::trace always queries [1e-4, inf), and every
+ * secondary ray follows the reference.  Per ray 64 B cross to the device and
+ * 24 B back, in chunks of bounded size.  flags: RT_FLAG_NONE or
+ * RT_FLAG_NO_CULL (byte-identical results; RT_FLAG_NO_BVH / RT_FLAG_FORCE_BVH
+ * have no effect); RT_FLAG_FP32 and RT_FLAG_COUNT_OPS are RT_ERR_UNSUPPORTED,
+ * as is a scene or recursion depth beyond the device stacks (the frames' own
+ * limit and message).  n == 0 is RT_OK without a launch.  stats (may be NULL):
+ * rays_intersect / rays_occluded are the Scene::intersect / Scene::occluded
+ * calls that tracing these n rays makes (the quantities a frame reports),
+ * rays_traced their sum, pixels 0, ms_kernel, ms_total.  Uses the current HIP
+ * device and shares its resident scene copy with the frames and the other
+ * queries; waits for an open frame of the device; blocks until done. */
+int rt_query_radiance(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, double* rgb_host,
+                      rt_stats* stats);
+/* The same with rays and colours already on the device, enqueued on
+ * hip_stream (NULL = the default stream); blocks until done. */
+int rt_query_radiance_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, double* rgb_dev,
                              void* hip_stream, rt_stats* stats);
 
 /* ------------------------------------------------------------ host I/O */

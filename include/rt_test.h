@@ -62,11 +62,21 @@ int rt_test_kernel_name(const struct rt_scene* s, int mode, int flags, char* out
  * refused here too.  Host only. */
 int rt_test_query_kernel_name(const struct rt_scene* s, int kind, int flags, char* out, int cap);
 
+/* The same for a radiance query (rt_query_radiance; e.g. "rtd::k_radiance<false,
+ * false, true, true>"): frame_plan.hpp pick_radiance_variant looked up in the
+ * radiance table.  Host only. */
+int rt_test_radiance_kernel_name(const struct rt_scene* s, int flags, char* out, int cap);
+/* Row `index` of the radiance launch table `table` (0 rtd, 1 rtdb), as
+ * rt_test_kernel_row below reads the other tables: "ns::name" into out;
+ * RT_OK, or RT_ERR_INVALID_ARG past the end or for another table.  Host only. */
+int rt_test_radiance_kernel_row(int table, int index, char* out, int cap);
+
 /* The launch log: which kernels ran.  rt_test_kernel_name above is the plan
  * for a frame whose wave BVH is on and untimed; the frame itself may drop the
  * BVH (its trial frames) or launch the timed build of a paper kernel (the
  * first frame of a scene and shape).  The log records what the launchers of
- * rt_kernels.hpp / rt_query_kernels.hpp were asked for, host side only.
+ * rt_kernels.hpp / rt_query_kernels.hpp / rt_radiance_kernels.hpp were asked
+ * for, host side only.
  * on != 0: clear the log and start recording; 0: stop.  Process-wide,
  * thread-safe; while recording is off a launch pays one relaxed atomic load. */
 int rt_test_launch_log(int on);

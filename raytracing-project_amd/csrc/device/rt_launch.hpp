@@ -132,7 +132,18 @@ struct QueryParams {
     rt_hit* hits;
     uint8_t* mask;
 };
-enum { kQueryIsect = 0, kQueryOccl = 1 };   // query kinds (k_query_isect / k_query_occl)
+enum { kQueryIsect = 0, kQueryOccl = 1, kQueryRadiance = 2 };   // query kinds (k_query_isect / k_query_occl / k_radiance)
+
+// A batch of radiance queries (rt_query_radiance): ray i of rays[0, n) is lane
+// i % 64 of wave i / 64, rgb[3i .. 3i + 2] its colour (Tracer::trace); tmin /
+// tmax of the rays are not read.  counters: the frames' kCounterSlots x
+// kCounterWords slots (words 0, 1: the Scene::intersect / Scene::occluded calls).
+struct RadianceParams {
+    const rt_ray* rays;
+    size_t n;
+    double* rgb;
+    unsigned long long* counters;
+};
 
 // Paper mode's output alphabet (tracer.cpp:258-281): every pixel is grey
 // (r = g = b) and a function of the edge strength - the max of the constants
@@ -178,8 +189,10 @@ void note_launch(const char* ns, const char* name);
 // (frame_plan.hpp).  launch_*: hipErrorInvalidDeviceFunction when the
 // namespace has no kernel for the variant.  launch_query / query_kernel: the
 // ray-query kernels (rt_query_kernels.hpp, their own translation units; rtf
-// has none).  *_row_name(i): row i of the namespace's table, nullptr past its
-// end (rt_test_kernel_row).
+// has none).  launch_radiance / radiance_kernel: the radiance-query kernels
+// (rt_radiance_kernels.hpp, likewise; rtd and rtdb only, rtf defines none).
+// *_row_name(i): row i of the namespace's table, nullptr past its end
+// (rt_test_kernel_row, rt_test_radiance_kernel_row).
 #define RT_DECLARE_LAUNCHERS(NS)                                                                                  \
     namespace NS {                                                                                                \
     hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,               \
@@ -198,6 +211,10 @@ void note_launch(const char* ns, const char* name);
     const char* paper_row_name(int i);                                                                            \
     const char* finish_row_name(int i);                                                                           \
     const char* query_row_name(int i);                                                                            \
+    hipError_t launch_radiance(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,          \
+                               const rtamd::RadianceParams& P);                                                   \
+    rtamd::KernelEntry radiance_kernel(const rtamd::KernelVariant& v);                                            \
+    const char* radiance_row_name(int i);                                                                         \
     }
 RT_DECLARE_LAUNCHERS(rtd)
 RT_DECLARE_LAUNCHERS(rtf)
@@ -234,6 +251,16 @@ inline hipError_t launch_query(const KernelVariant& v, int kind, hipStream_t st,
 inline KernelEntry query_kernel(const KernelVariant& v, int kind) {
     return v.ns == KernelVariant::kRtf ? rtf::query_kernel(v, kind)
                                        : v.ns == KernelVariant::kRtdb ? rtdb::query_kernel(v, kind) : rtd::query_kernel(v, kind);
+}
+// (pick_radiance_variant never picks rtf: no FP32 radiance queries)
+inline hipError_t launch_radiance(const KernelVariant& v, hipStream_t st, const SceneView& V, const RadianceParams& P) {
+    return v.ns == KernelVariant::kRtf ? hipErrorInvalidDeviceFunction
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_radiance(v, st, V, P)
+                                                                      : rtd::launch_radiance(v, st, V, P);
+}
+inline KernelEntry radiance_kernel(const KernelVariant& v) {
+    return v.ns == KernelVariant::kRtf ? KernelEntry{nullptr, nullptr}
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::radiance_kernel(v) : rtd::radiance_kernel(v);
 }
 inline int trace_block_threads(const KernelVariant& v, bool paper) {
     return v.ns == KernelVariant::kRtf ? rtf::kernel_block_threads(paper)

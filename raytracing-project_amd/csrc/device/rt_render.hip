@@ -16,6 +16,9 @@
 // Ray queries (rt_query_intersect / rt_query_occluded, Scene::intersect /
 // Scene::occluded for caller-given rays, scene.cpp:10-42): query_impl here,
 // on the frames' workspace and resident scene; kernels in rt_query_kernels.hpp.
+// Radiance queries (rt_query_radiance, Tracer::trace for caller-given rays,
+// tracer.cpp:12-73): the same query_impl, with the frames' ray counters;
+// kernels in rt_radiance_kernels.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -46,6 +49,7 @@ using rtamd::kCounterSlots;
 using rtamd::kCounterWords;
 using rtamd::PaperParams;
 using rtamd::QueryParams;
+using rtamd::RadianceParams;
 using rtamd::SceneView;
 using rtamd::StdParams;
 
@@ -173,7 +177,7 @@ struct Workspace {
     rtamd::JitterCache jcache{jitter_alloc, jitter_free};
     DBuf ckpt, jscratch, counters;
     DBuf paper_i, paper_d, paper_aux, fb;
-    DBuf q_rays, q_hits, q_mask;              // ray queries from host memory: one chunk's rays / hits / flags
+    DBuf q_rays, q_hits, q_mask, q_rgb;       // ray queries from host memory: one chunk's rays / hits / flags / colours
     rtamd::JitterTable jtab;                  // mt19937(12345) checkpoint table (resident)
     rtamd::JitterJob jjob;
     rtamd::PinnedArena up;                    // page-locked staging of a frame's uploads (pinned.hpp)
@@ -437,6 +441,31 @@ void scene_view(const Workspace& ws, const rt_scene_desc& d, int flags, bool fp3
     S.bg_mat = d.n_materials;
 }
 
+// The page-locked words k_reduce_counters stores into: at least host_words
+// (the previous frame's or query's readback is done)
+int ensure_ctr_host(Workspace& ws, size_t host_words) {
+    if (ws.ctr_host && ws.ctr_host_words >= host_words) return RT_OK;
+    if (ws.ctr_host) (void)hipHostFree(ws.ctr_host);
+    ws.ctr_host = nullptr;
+    ws.ctr_host_words = 0;
+    rtamd::SetupTimer tm(rtamd::kSetupPinned);
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ws.ctr_host), host_words * sizeof(unsigned long long),
+                          hipHostMallocDefault));
+    ws.ctr_host_words = host_words;
+    return RT_OK;
+}
+
+// The ray / op counter slots, zero on st before a frame's or a radiance
+// query's first launch (the last k_reduce_counters may have left them zero)
+int counters_ready(Workspace& ws, hipStream_t st) {
+    const size_t ctr_bytes = (size_t)kCounterSlots * kCounterWords * sizeof(unsigned long long);
+    const void* before = ws.counters.p;
+    HIP_TRY(ws.counters.ensure(ctr_bytes));
+    if (!ws.counters_zero || ws.counters.p != before) HIP_TRY(hipMemsetAsync(ws.counters.p, 0, ctr_bytes, st));
+    ws.counters_zero = false;   // (until the reduction has run)
+    return RT_OK;
+}
+
 int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int32_t* rows_host, int n_rows,
                 hipStream_t st, rt_frame** out) {
     const auto t_start = std::chrono::steady_clock::now();
@@ -494,12 +523,9 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
         rtamd::SetupTimer tm(rtamd::kSetupStreams);
         for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
     }
-    const size_t ctr_bytes = (size_t)kCounterSlots * kCounterWords * sizeof(unsigned long long);
     {
-        const void* before = ws.counters.p;
-        HIP_TRY(ws.counters.ensure(ctr_bytes));
-        if (!ws.counters_zero || ws.counters.p != before) HIP_TRY(hipMemsetAsync(ws.counters.p, 0, ctr_bytes, st));
-        ws.counters_zero = false;   // (until this frame's reduction has run)
+        const int rv = counters_ready(ws, st);
+        if (rv != RT_OK) return rv;
     }
 
     SceneView& S = f->S;
@@ -745,14 +771,9 @@ int frame_end_body(rt_frame* f, rt_stats* stats) {
     HIP_TRY(hipEventRecord(ws.ev[2], st));
     const int n_groups = f->paper_calls.list_used() / 8;
     const size_t host_words = kCounterWords + ((size_t)n_groups + 1) / 2;
-    if (!ws.ctr_host || ws.ctr_host_words < host_words) {
-        if (ws.ctr_host) (void)hipHostFree(ws.ctr_host);   // (the previous frame's readback is done)
-        ws.ctr_host = nullptr;
-        ws.ctr_host_words = 0;
-        rtamd::SetupTimer tm(rtamd::kSetupPinned);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ws.ctr_host), host_words * sizeof(unsigned long long),
-                              hipHostMallocDefault));
-        ws.ctr_host_words = host_words;
+    {
+        const int rv = ensure_ctr_host(ws, host_words);
+        if (rv != RT_OK) return rv;
     }
     unsigned long long* ctr = ws.counters.as<unsigned long long>();
     const bool timed = f->timed;   // (some launch of this frame stored its waves' ticks)
@@ -833,17 +854,21 @@ int render_rows_impl(const rt_scene* s, int W, int H, int mode, int flags, const
 constexpr size_t kQueryLaunchRays = (size_t)1 << 30;
 constexpr size_t kQueryChunkRays = (size_t)1 << 20;
 
-// rt_query_{intersect,occluded}[_device]: kind rtamd::kQueryIsect / kQueryOccl.
-// host: rays / hits / mask are host memory, moved through the workspace's
-// chunk buffers; else device memory, traced in place on st.  Holds the
-// workspace lock like a frame, and returns with st drained.
+// rt_query_{intersect,occluded,radiance}[_device]: kind rtamd::kQueryIsect /
+// kQueryOccl / kQueryRadiance (results: hits and mask / mask / rgb, three
+// doubles per ray).  host: rays and results are host memory, moved through the
+// workspace's chunk buffers; else device memory, traced in place on st.  Holds
+// the workspace lock like a frame, and returns with st drained.  A radiance
+// query counts its Scene::intersect / Scene::occluded calls in the frames'
+// counter slots: zeroed before its first launch, reduced after its last.
 int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays, size_t n, int flags, rt_hit* hits,
-               uint8_t* mask, bool host, hipStream_t st, rt_stats* stats) {
+               uint8_t* mask, double* rgb, bool host, hipStream_t st, rt_stats* stats) {
     const auto t_start = SClock::now();
     const auto fail = [what](const char* msg, int rc) {
         rtamd::set_last_error(std::string(what) + ": " + msg);
         return rc;
     };
+    const bool isect = kind == rtamd::kQueryIsect, radiance = kind == rtamd::kQueryRadiance;
     if (!s) return fail("scene is NULL", RT_ERR_INVALID_ARG);
     if (flags & ~(RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH))
         return fail("unknown flag bits", RT_ERR_INVALID_ARG);
@@ -857,7 +882,7 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
     }
     if (n == 0) return RT_OK;
     if (!rays) return fail("rays is NULL", RT_ERR_INVALID_ARG);
-    if (kind == rtamd::kQueryIsect ? !hits : !mask) return fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
+    if (radiance ? !rgb : isect ? !hits : !mask) return fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
     const rt_scene_desc& d = *rt_scene_get_desc(s);
@@ -879,7 +904,8 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
     }
     rtamd::KernelVariant kv;
     {
-        const int rv = rtamd::pick_query_variant(ws.sc.cs, d, flags, &kv);
+        const int rv = radiance ? rtamd::pick_radiance_variant(ws.sc.cs, d, flags, &kv)
+                                : rtamd::pick_query_variant(ws.sc.cs, d, flags, &kv);
         if (rv != RT_OK) return rv;
     }
     SceneView S;
@@ -889,12 +915,17 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
         rtamd::SetupTimer tm(rtamd::kSetupStreams);
         for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
     }
-    const bool isect = kind == rtamd::kQueryIsect;
+    if (radiance) {
+        int rv = counters_ready(ws, st);
+        if (rv == RT_OK) rv = ensure_ctr_host(ws, kCounterWords);
+        if (rv != RT_OK) return rv;
+    }
     const size_t chunk = host ? std::min(n, kQueryChunkRays) : n;
     if (host) {
         HIP_TRY(ws.q_rays.ensure(chunk * sizeof(rt_ray)));
         if (isect) HIP_TRY(ws.q_hits.ensure(chunk * sizeof(rt_hit)));
-        if (!isect || mask) HIP_TRY(ws.q_mask.ensure(chunk));
+        if (mask) HIP_TRY(ws.q_mask.ensure(chunk));
+        if (radiance) HIP_TRY(ws.q_rgb.ensure(chunk * 3 * sizeof(double)));
     }
     double ms_kernel = 0.0;
     for (size_t c0 = 0; c0 < n; c0 += chunk) {
@@ -902,29 +933,53 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
         const rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays + c0;
         rt_hit* d_hits = !isect ? nullptr : host ? ws.q_hits.as<rt_hit>() : hits + c0;
         uint8_t* d_mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask + c0;
+        double* d_rgb = !radiance ? nullptr : host ? ws.q_rgb.as<double>() : rgb + 3 * c0;
         if (host) HIP_TRY(hipMemcpyAsync(ws.q_rays.p, rays + c0, cn * sizeof(rt_ray), hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(ws.ev[1], st));
         for (size_t l0 = 0; l0 < cn; l0 += kQueryLaunchRays) {
-            QueryParams P;
-            P.n = std::min(kQueryLaunchRays, cn - l0);
-            P.rays = d_rays + l0;
-            P.hits = d_hits ? d_hits + l0 : nullptr;
-            P.mask = d_mask ? d_mask + l0 : nullptr;
-            HIP_TRY(rtamd::launch_query(kv, kind, st, S, P));
+            const size_t ln = std::min(kQueryLaunchRays, cn - l0);
+            if (radiance) {
+                RadianceParams P;
+                P.n = ln;
+                P.rays = d_rays + l0;
+                P.rgb = d_rgb + 3 * l0;
+                P.counters = ws.counters.as<unsigned long long>();
+                HIP_TRY(rtamd::launch_radiance(kv, st, S, P));
+            } else {
+                QueryParams P;
+                P.n = ln;
+                P.rays = d_rays + l0;
+                P.hits = d_hits ? d_hits + l0 : nullptr;
+                P.mask = d_mask ? d_mask + l0 : nullptr;
+                HIP_TRY(rtamd::launch_query(kv, kind, st, S, P));
+            }
         }
         HIP_TRY(hipEventRecord(ws.ev[2], st));
         if (host) {
             if (isect) HIP_TRY(hipMemcpyAsync(hits + c0, d_hits, cn * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
             if (mask) HIP_TRY(hipMemcpyAsync(mask + c0, d_mask, cn, hipMemcpyDeviceToHost, st));
+            if (radiance) HIP_TRY(hipMemcpyAsync(rgb + 3 * c0, d_rgb, cn * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
         }
         // (the chunk buffers and the events are reused by the next chunk)
         HIP_TRY(hipStreamSynchronize(st));
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) ms_kernel += ms;
     }
+    uint64_t n_isect = isect ? n : 0, n_occl = radiance || isect ? 0 : n;
+    if (radiance) {
+        // the slots' sums, as a frame's end reads them (and the slots are left zero)
+        hipLaunchKernelGGL(k_reduce_counters, dim3(kCounterWords), dim3(64), 0, st, ws.counters.as<unsigned long long>(),
+                           ws.ctr_host, nullptr, 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        ws.counters_zero = true;
+        n_isect = ((volatile unsigned long long*)ws.ctr_host)[0];
+        n_occl = ((volatile unsigned long long*)ws.ctr_host)[1];
+    }
     if (stats) {
-        (isect ? stats->rays_intersect : stats->rays_occluded) = n;
-        stats->rays_traced = n;
+        stats->rays_intersect = n_isect;
+        stats->rays_occluded = n_occl;
+        stats->rays_traced = n_isect + n_occl;
         stats->ms_kernel = ms_kernel;
         stats->ms_total = ms_since(t_start);
     }
@@ -1035,7 +1090,7 @@ int rtamd::release_device_workspaces(int min_slot) {
                         &w->wobjs, &w->wctab, &w->worig, &w->wchunk,
                         &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->ckpt,
                         &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime,
-                        &w->q_rays, &w->q_hits, &w->q_mask})
+                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb})
             b->release();
         w->jtab.release();
         w->jcache.release();   // every cached entry and the uncached buffer (the hit / miss counts stay)
@@ -1245,26 +1300,38 @@ extern "C" int rt_render(const rt_scene* s, int W, int H, int mode, int flags, d
 
 extern "C" int rt_query_intersect(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, rt_hit* hits_host,
                                   uint8_t* hit_mask_host, rt_stats* stats) {
-    return query_impl("rt_query_intersect", s, rtamd::kQueryIsect, rays_host, n, flags, hits_host, hit_mask_host, true,
-                      nullptr, stats);
+    return query_impl("rt_query_intersect", s, rtamd::kQueryIsect, rays_host, n, flags, hits_host, hit_mask_host, nullptr,
+                      true, nullptr, stats);
 }
 
 extern "C" int rt_query_occluded(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, uint8_t* occluded_host,
                                  rt_stats* stats) {
-    return query_impl("rt_query_occluded", s, rtamd::kQueryOccl, rays_host, n, flags, nullptr, occluded_host, true,
+    return query_impl("rt_query_occluded", s, rtamd::kQueryOccl, rays_host, n, flags, nullptr, occluded_host, nullptr, true,
                       nullptr, stats);
 }
 
 extern "C" int rt_query_intersect_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, rt_hit* hits_dev,
                                          uint8_t* hit_mask_dev, void* hip_stream, rt_stats* stats) {
     return query_impl("rt_query_intersect_device", s, rtamd::kQueryIsect, rays_dev, n, flags, hits_dev, hit_mask_dev,
-                      false, (hipStream_t)hip_stream, stats);
+                      nullptr, false, (hipStream_t)hip_stream, stats);
 }
 
 extern "C" int rt_query_occluded_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags,
                                         uint8_t* occluded_dev, void* hip_stream, rt_stats* stats) {
-    return query_impl("rt_query_occluded_device", s, rtamd::kQueryOccl, rays_dev, n, flags, nullptr, occluded_dev, false,
-                      (hipStream_t)hip_stream, stats);
+    return query_impl("rt_query_occluded_device", s, rtamd::kQueryOccl, rays_dev, n, flags, nullptr, occluded_dev, nullptr,
+                      false, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_query_radiance(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, double* rgb_host,
+                                 rt_stats* stats) {
+    return query_impl("rt_query_radiance", s, rtamd::kQueryRadiance, rays_host, n, flags, nullptr, nullptr, rgb_host, true,
+                      nullptr, stats);
+}
+
+extern "C" int rt_query_radiance_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, double* rgb_dev,
+                                        void* hip_stream, rt_stats* stats) {
+    return query_impl("rt_query_radiance_device", s, rtamd::kQueryRadiance, rays_dev, n, flags, nullptr, nullptr, rgb_dev,
+                      false, (hipStream_t)hip_stream, stats);
 }
 
 extern "C" int rt_scatter_rows_device(const double* src_dev, const int32_t* rows_dev, int n_rows, int W,

@@ -132,6 +132,26 @@ int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flag
     return RT_OK;
 }
 
+int pick_radiance_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out) {
+    int rc = check_query_flags(flags);
+    if (rc != RT_OK) return rc;
+    KernelVariant v;
+    for (int i = 0; i < d.n_materials; ++i)
+        if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) v.secondary = true;
+    if (d.recursion_limit < 2) v.secondary = false;   // (as pick_variant)
+    bool big = false;
+    rc = stack_tier(cs, d, v.secondary ? d.recursion_limit - 1 : 0, false, &big);
+    if (rc != RT_OK) return rc;
+    v.ns = big ? KernelVariant::kRtdb : KernelVariant::kRtd;
+    v.eager = big || cs.has_eager;
+    v.deep = v.eager || cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
+    if (v.eager) v.secondary = true;   // (the general row: the only eager one)
+    static const bool plain_on = env_on("RT_PLAIN");
+    v.plain = !v.deep && plain_on && plain_scene(cs);
+    *out = v;
+    return RT_OK;
+}
+
 // ----------------------------------------------------------------- dist plan
 int strip_height(int mode) { return mode == RT_MODE_PAPER ? RT_PAPER_STRIP_ROWS : RT_STRIP_ROWS; }
 

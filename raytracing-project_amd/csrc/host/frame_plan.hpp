@@ -71,6 +71,17 @@ int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int 
 int check_query_flags(int flags);
 int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
 
+// The variant a radiance query (rt_query_radiance: Tracer::trace of caller-given
+// rays) of (scene, flags) launches: check_query_flags first, then
+// pick_variant's standard-mode rules with per-lane culls forced (wv = 0, as
+// for the other queries).  secondary is the frame's, and the stack tiers count
+// the frame's recursion frames (recursion_limit - 1 when secondary), so a
+// scene whose frames need the big stacks takes them here too.  Eager scenes
+// (and every big-stack one) take the general kernel with secondary set
+// whatever the materials say: its loop never descends without a reflecting or
+// refracting hit, and the radiance table has no other eager row.
+int pick_radiance_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
+
 // ----------------------------------------------------------------- dist plan
 constexpr int kChunks = 4;   // pipeline units per rank (chunk k gathered while k+1 is traced)
 // Paper frames gather one code byte per pixel, so their chunks hide little

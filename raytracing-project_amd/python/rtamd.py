@@ -193,6 +193,13 @@ def amd_lib():
             lib.rt_query_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                                      C.c_void_p, C.POINTER(Stats)]
             lib.rt_test_query_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+        if hasattr(lib, "rt_query_radiance"):   # (absent only in RTAMD_LIB builds of older sources)
+            lib.rt_query_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                              C.POINTER(Stats)]
+            lib.rt_query_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(Stats)]
+            lib.rt_test_radiance_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+            lib.rt_test_radiance_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
         lib.rt_device_count.restype = C.c_int
         lib.rt_render_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                         C.POINTER(Stats)]
@@ -719,6 +726,56 @@ def query_kernel_name(scene: Scene, kind: int, flags: int = RT_FLAG_NONE) -> tup
     return rc, buf.value.decode()
 
 
+def query_radiance(scene: Scene, origins, dirs, flags: int = RT_FLAG_NONE, stats: Stats | None = None) -> np.ndarray:
+    """rt_query_radiance: Tracer::trace (the radiance along the ray) of every
+    ray, as an (n, 3) float64 array.  tmin / tmax play no part."""
+    rays = make_rays(origins, dirs)
+    n = len(rays)
+    rgb = np.zeros((n, 3), dtype=np.float64)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_radiance(scene.handle, rays.ctypes.data_as(C.c_void_p), n, flags,
+                                     rgb.ctypes.data_as(C.c_void_p), C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return rgb
+
+
+def query_radiance_device(scene: Scene, rays_dev: DeviceBuffer, n: int, rgb_dev: DeviceBuffer,
+                          flags: int = RT_FLAG_NONE, stream: Stream | None = None,
+                          stats: Stats | None = None) -> None:
+    """rt_query_radiance_device: the first n rt_ray records of rays_dev into
+    the first 3n doubles of rgb_dev, on `stream` (None: the default stream)."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize or rgb_dev.nbytes < n * 24:
+        raise ValueError("query_radiance_device: a buffer is too small for n rays")
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_radiance_device(scene.handle, rays_dev.ptr, n, flags, rgb_dev.ptr,
+                                            stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def radiance_kernel_name(scene: Scene, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
+    """rt_test_radiance_kernel_name: (status, "ns::kernel") of the kernel a
+    radiance query of this scene and flags launches.  Host only."""
+    buf = C.create_string_buffer(160)
+    rc = amd_lib().rt_test_radiance_kernel_name(scene.handle, flags, buf, 160)
+    return rc, buf.value.decode()
+
+
+RADIANCE_TABLES = ("rtd radiance", "rtdb radiance")
+
+
+def radiance_rows(table: int) -> list[str]:
+    """rt_test_radiance_kernel_row: the rows ("ns::kernel") of radiance launch
+    table `table` (an index into RADIANCE_TABLES).  Host only."""
+    lib = amd_lib()
+    buf = C.create_string_buffer(160)
+    out = []
+    while lib.rt_test_radiance_kernel_row(table, len(out), buf, 160) == RT_OK:
+        out.append(buf.value.decode())
+    return out
+
+
 def render_multi(scene: Scene, width: int, height: int, mode: int, n_gpus: int, flags: int = RT_FLAG_NONE,
                  stats: Stats | None = None) -> np.ndarray:
     """rt_render_multi: the frame over n_gpus devices of this process."""
@@ -843,6 +900,67 @@ def oracle_render(scene: Scene, width: int, height: int, mode: int, row0: int = 
     if rc != 0:
         raise RuntimeError("oracle_render_rows failed")
     return fb, st
+
+
+def oracle_trace(scene: Scene, origins, dirs):
+    """Tracer::trace(Ray(o, d)) of every ray through the oracle: (rgb (n, 3),
+    n_intersect (n,), n_occluded (n,)), the colour and the Scene::intersect /
+    Scene::occluded calls of each ray.  TEST ONLY.
+
+    Per ray, a 1x1 standard frame of a copy of the scene whose camera has eye
+    = o, P = o + d and a zero-size screen: generate_ray_subpixel then maps
+    every jitter draw to P (camera.h:68-78), so the frame is the mean of 8
+    evaluations of Tracer::trace(Ray(o, P - o)) and its ray counts are 8x the
+    ray's own.  The ray the oracle traces is therefore (o + d) - o as rounded
+    in float64: hand the GPU oracle_trace_dirs(origins, dirs)."""
+    lib = oracle_lib()
+    o = np.asarray(origins, dtype=np.float64)
+    d = np.asarray(dirs, dtype=np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and dirs must both be (n, 3) arrays, got {o.shape} and {d.shape}")
+    n = len(o)
+    P = o + d
+    desc = SceneDesc.from_buffer_copy(scene.desc)   # (shares the scene's arrays: keep `scene` alive)
+    desc.camera.Lx = desc.camera.Ly = 0.0
+    desc.camera.dpi = 1
+    rgb, ni, no = np.zeros((n, 3)), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    px = np.zeros(3)
+    pp, st = px.ctypes.data_as(_dp), OracleStats()
+    for k in range(n):
+        desc.camera.eye[:] = o[k].tolist()
+        desc.camera.P[:] = P[k].tolist()
+        if lib.oracle_render_rows(C.byref(desc), 1, 1, RT_MODE_STANDARD, 0, 1, pp, C.byref(st), 1) != 0:
+            raise RuntimeError("oracle_render_rows failed")
+        assert st.rays_intersect % 8 == 0 and st.rays_occluded % 8 == 0, (k, st.rays_intersect, st.rays_occluded)
+        rgb[k], ni[k], no[k] = px, st.rays_intersect // 8, st.rays_occluded // 8
+    return rgb, ni, no
+
+
+def oracle_frame_rays(scene: Scene):
+    """The standard frame's own 8 W H jittered rays (tracer.cpp:284-293:
+    oracle_jitter + Camera::generate_ray_subpixel through the oracle) in frame
+    order: (origins, dirs), each (H, W, 8, 3), output row first, samples in
+    the order the frame sums them.  TEST ONLY."""
+    lib = oracle_lib()
+    W, H = scene.width, scene.height
+    jit = np.zeros(16 * W * H)
+    lib.oracle_jitter(0, len(jit), jit.ctypes.data_as(_dp))
+    jit = jit.reshape(H, W, 8, 2)   # (loop row, x, sample, dx / dy)
+    o, d = np.zeros((H, W, 8, 3)), np.zeros((H, W, 8, 3))
+    o3, d3 = (C.c_double * 3)(), (C.c_double * 3)()
+    desc = scene.desc_ptr
+    for y in range(H):   # loop row y is output row H - 1 - y (tracer.cpp:297)
+        for x in range(W):
+            for s in range(8):
+                lib.oracle_camera_ray(desc, x, y, jit[y, x, s, 0], jit[y, x, s, 1], 1, o3, d3)
+                o[H - 1 - y, x, s], d[H - 1 - y, x, s] = tuple(o3), tuple(d3)
+    return o, d
+
+
+def oracle_trace_dirs(origins, dirs) -> np.ndarray:
+    """The directions oracle_trace really traces: (o + d) - o in float64."""
+    o = np.asarray(origins, dtype=np.float64)
+    return (o + np.asarray(dirs, dtype=np.float64)) - o
 
 
 def oracle_primary_hits(scene: Scene) -> np.ndarray:

@@ -1011,6 +1011,26 @@ def kernel_recipes() -> list[Recipe]:
     return out
 
 
+def radiance_recipes() -> list[Recipe]:
+    """One Recipe (row, scene name, flags; mode, frame unused) per row of the
+    radiance launch tables (rt_test.h rt_test_radiance_kernel_row):
+    k_radiance<E, D, SEC, PL>.  The SEC rows' scenes reflect or refract, so a
+    bounce really runs.  tests/test_radiance_plan.py holds this list against
+    the tables, tests/test_gpu_radiance.py queries every entry."""
+    out = []
+    b = lambda v: "true" if v else "false"   # noqa: E731
+    for ns, e, d, sec, pl, scene in (("rtd", 1, 1, 1, 0, "shading/lights33_xform"),
+                                     ("rtd", 0, 1, 1, 0, "dir/reflect_refract_sun"),
+                                     ("rtd", 0, 1, 0, 0, "dir/cfg2_sun_back"),
+                                     ("rtd", 0, 0, 1, 0, "torture/reflect_refract"),
+                                     ("rtd", 0, 0, 0, 0, "cfg/4"),
+                                     ("rtd", 0, 0, 1, 1, "cfg/5"),
+                                     ("rtd", 0, 0, 0, 1, "cfg/3"),
+                                     ("rtdb", 1, 1, 1, 0, "deep/mirrors_rec24")):
+        out.append(Recipe(f"{ns}::k_radiance<{b(e)}, {b(d)}, {b(sec)}, {b(pl)}>", scene, 0, 0, 0))
+    return out
+
+
 def row_timed(row: str, timed: bool) -> str:
     """A paper primary row's name with its T argument set (k_paper_primary<E,
     D, C[, T]>: the untimed rows leave T out; k_paper_primary_lean<C, WV, T,
