@@ -2417,7 +2417,15 @@ __device__ __forceinline__ bool cone_touch(const float* g, const Cone& K) {
 // loop would: of two objects hitting at the same t, the later (in the
 // reference's order) wins if it accepts t == tmax (spheres, half-spaces,
 // pokeballs: rtamd::accepts_tie), else the earlier one.
-template <bool EAGER, bool DEEP, bool BV = false, bool LEAD = false, class CT>
+//
+// CAM: the camera call (trace()): every ray starts at the eye, so the bundle's
+// origin spread rho is exactly 0 (the f32 origins are equal bit for bit, and
+// a non-finite eye has no cone) and its reduction is skipped.  RT_CAM_RHO0=0
+// computes it as for any other bundle (A/B switch).
+#ifndef RT_CAM_RHO0
+#define RT_CAM_RHO0 1
+#endif
+template <bool EAGER, bool DEEP, bool BV = false, bool LEAD = false, bool CAM = false, class CT>
 __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin, real tmax, real& t_best,
                                      DHit& best, bool wave_ok, CT& cnt, bool valid = true) {
     cnt.pb(PH_WAVE_SETUP);
@@ -2434,12 +2442,15 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
     const bool cone = S.cull && wave_ok && exec_full() && !__any(valid && !fin) && tmin >= RV(0.0);
     const float ox = rdlane_f(fr.ox, f), oy = rdlane_f(fr.oy, f), oz = rdlane_f(fr.oz, f);
     const float ax = rdlane_f(fr.dx, f), ay = rdlane_f(fr.dy, f), az = rdlane_f(fr.dz, f);
-    const float do2 = valid ? (fr.ox - ox) * (fr.ox - ox) + (fr.oy - oy) * (fr.oy - oy) + (fr.oz - oz) * (fr.oz - oz)
-                            : 0.0f;
     // 1 - cos(angle to the axis), >= 0 up to rounding
     const float dc = valid ? __builtin_fmaxf(0.0f, 1.0f - __builtin_fmaf(fr.dx, ax, __builtin_fmaf(fr.dy, ay, fr.dz * az)))
                            : 0.0f;
-    const float rho = cone ? sqrt_cull(__uint_as_float(wave_max_u32(__float_as_uint(do2)))) : 0.0f;
+    float rho = 0.0f;
+    if constexpr (!(CAM && RT_CAM_RHO0)) {
+        const float do2 = valid ? (fr.ox - ox) * (fr.ox - ox) + (fr.oy - oy) * (fr.oy - oy) + (fr.oz - oz) * (fr.oz - oz)
+                                : 0.0f;
+        rho = cone ? sqrt_cull(__uint_as_float(wave_max_u32(__float_as_uint(do2)))) : 0.0f;
+    }
     const float dcm = cone ? __uint_as_float(wave_max_u32(__float_as_uint(dc))) + 4e-6f : 2.0f;   // rounding of unit dots
     const float cth = 1.0f - dcm;
     const bool wide = !(cth > 0.0f);   // a bundle wider than 90 degrees (or no cone): no culling
@@ -3044,7 +3055,7 @@ __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect
             // miss lanes stay in shade() (valid = false) so that the wave
             // stays fully active for the wave-level shadow queries
             cnt.pb(PH_PRIMARY);
-            const bool hit = scene_intersect_wave<EAGER, DEEP, (WV == 2)>(S, r, RV(1e-4), RT_INF, ht, h,
+            const bool hit = scene_intersect_wave<EAGER, DEEP, (WV == 2), false, true>(S, r, RV(1e-4), RT_INF, ht, h,
                                                                __builtin_amdgcn_read_exec() == ~0ull, cnt);
             cnt.pe(PH_PRIMARY);
             if (!__any(hit)) return background(S);

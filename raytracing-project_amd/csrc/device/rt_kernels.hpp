@@ -93,7 +93,7 @@ __device__ __forceinline__ void flush_counters(unsigned long long* ctr, uint32_t
     if (lane == 0)
 #pragma unroll
         for (int k = 0; k < NW; ++k) red(wave)[k] = v[k];
-    if constexpr (NWAVES > 1) __syncthreads();
+    __syncthreads();   // (a one-wave group too: lane 0's LDS writes are fenced before the wave reads them)
     if (threadIdx.x < NW) {
         unsigned long long sum = 0;
 #pragma unroll
