@@ -101,6 +101,21 @@ int rt_test_kernel_row(int table, int index, char* out, int cap);
  * two to be bit-identical. */
 int rt_test_div3(const double* a_host, const double* b_host, int n, double* div3_host, double* plain_host);
 
+/* GPU: the fused square root + division of the device code (rt_device.hpp
+ * norm3) next to the compiler's own operations on the same vectors, one lane
+ * per vector v_host[3i..3i+2], 256-thread blocks in input order (so the caller
+ * decides which vectors share a wave).  L_host[i], q_host[3i+k]: norm3's |v|
+ * and v[k] / |v|; plainL_host, plainq_host: __builtin_sqrt of the same sum of
+ * squares and `/` in the same kernel; fast_host[i] = 1 if lane i's wave took
+ * the fused path (every lane of the wave in range), 0 if it took sqrt + div3.
+ * Tests require norm3 and plain to be bit-identical.  Returns an rt_status. */
+int rt_test_norm3(const double* v_host, int n, double* L_host, double* q_host, double* plainL_host,
+                  double* plainq_host, int* fast_host);
+
+/* GPU: out_host[3i..3i+2] = normalized(v_host[3i..3i+2]) (Dir3::normalized:
+ * v / |v|, or (0, 1, 0) when |v| <= 1e-6), launched like rt_test_norm3. */
+int rt_test_normalized(const double* v_host, int n, double* out_host);
+
 /* GPU: out_host[i] = pow_spec(x_host[i], y_host[i]), the device code's own
  * std::pow(rdotv, shininess) of the specular term (rt_device.hpp pow_spec,
  * shading.cpp:124), one lane per element, 256-thread blocks in input order (so

@@ -131,7 +131,92 @@ __device__ __forceinline__ auto div3(float a0, float a1, float a2, float b) {
     return F3{a0 / b, a1 / b, a2 / b};
 }
 
+// ------------------------------------------------- fused sqrt + division
+// RT_FUSED_NORM=1: a square root followed by three divisions by its result
+// (every normalisation, and the light direction tl / dist of shade()) shares
+// the root's refinement with the divisions.  Bit-identical to `__builtin_sqrt`
+// and `/` (tools/probe/norm3_check.c,
+// tests/test_gpu_norm3.py).  RT_FUSED_NORM=0 compiles sqrt_r + div3 at every
+// site (A/B switch; the float build always does).
+#ifndef RT_FUSED_NORM
+#define RT_FUSED_NORM 1
+#endif
+static_assert(!RT_FUSED_NORM || std::is_same_v<real, double>, "RT_FUSED_NORM is FP64 only (rt_kernels_f32.hip sets it to 0)");
+
+// The refinement core of the compiler's FP64 square root (`__builtin_sqrt` on
+// gfx950: v_rsq_f64, two multiplies, seven fma, in this order) without the
+// input scaling, the class test and the selects around it, which do nothing
+// for a normal s away from the exponent limits.  Returns RN(sqrt(s)); h is
+// the refined 1 / (2 sqrt(s)).
+__device__ __forceinline__ double sqrt_core(double s, double& h) {
+    const double y = __builtin_amdgcn_rsq(s);
+    double g = s * y;
+    h = y * 0.5;
+    const double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    const double d0 = __builtin_fma(-g, g, s);
+    g = __builtin_fma(d0, h, g);
+    const double d1 = __builtin_fma(-g, g, s);
+    return __builtin_fma(d1, h, g);
+}
+
+// (a0, a1, a2) / L for L = sqrt_core(s, h): the reciprocal starts from
+// y0 = 2h (1 / L to ~2^-47), takes one Newton step against the rounded L, and
+// each quotient is q = a y corrected once by its exact residual a - L q.
+// Equal to `/` bit for bit when 2^-600 <= |a_k| <= ~L <= 2^300 (nothing
+// underflows or overflows on the way); a zero numerator is excluded because
+// -0 would come out as +0.
+__device__ __forceinline__ D3 div3(double a0, double a1, double a2, double L, double h) {
+    const double y0 = h + h;
+    const double e = __builtin_fma(-L, y0, 1.0);
+    const double y = __builtin_fma(y0, e, y0);
+    auto quot = [&](double a) {
+        const double q = a * y;
+        const double r = __builtin_fma(-L, q, a);
+        return __builtin_fma(r, y, q);
+    };
+    return D3{quot(a0), quot(a1), quot(a2)};
+}
+
+struct N3 {
+    double L;
+    D3 q;
+    bool fast;
+};
+// today's path, out of line (one copy per kernel; inlined, the three one-by-one
+// divisions of div3's own fallback would sit at every site)
+__device__ __attribute__((noinline)) N3 sqrt_div3_general(double a0, double a1, double a2, double s) {
+    const double L = __builtin_sqrt(s);
+    return N3{L, div3(a0, a1, a2, L), false};
+}
+// L = sqrt(s) and a / L, for s = dot3(a, a) or that sum raised to a floor
+// (shade()'s d2), so |a_k| <= ~sqrt(s).  The fused path runs when every
+// active lane has 2^-600 <= s <= 2^600 and every |a_k| >= 2^-600 (NaN, +-inf
+// and +-0 fail these comparisons); otherwise the whole wave takes
+// sqrt_div3_general, so the branch is scalar.  live = false: a lane whose
+// result the caller discards does not vote (it gets the fused path's value for
+// whatever it holds).
+__device__ __forceinline__ N3 sqrt_div3(double a0, double a1, double a2, double s, bool live = true) {
+    constexpr double lo = 0x1p-600, hi = 0x1p600;
+    const bool ok = s >= lo && s <= hi && __builtin_fabs(a0) >= lo && __builtin_fabs(a1) >= lo &&
+                    __builtin_fabs(a2) >= lo;
+    if (!__all(ok || !live)) return sqrt_div3_general(a0, a1, a2, s);
+    double h;
+    const double L = sqrt_core(s, h);
+    return N3{L, div3(a0, a1, a2, L, h), true};
+}
+// |v| and v / |v|
+__device__ __forceinline__ N3 norm3(V3 v) { return sqrt_div3(v.x, v.y, v.z, dot3(v, v)); }
+
 // Dir3::normalized (core.h:95-101)
+#if RT_FUSED_NORM
+__device__ __forceinline__ V3 normalized(V3 v) {
+    const N3 r = norm3(v);
+    if (r.L > kEPS) return v3(r.q.x, r.q.y, r.q.z);
+    return v3(RV(0.0), RV(1.0), RV(0.0));
+}
+#else
 __device__ __forceinline__ V3 normalized(V3 v) {
     real L = sqrt_r(dot3(v, v));
     if (L > kEPS) {
@@ -140,6 +225,7 @@ __device__ __forceinline__ V3 normalized(V3 v) {
     }
     return v3(RV(0.0), RV(1.0), RV(0.0));
 }
+#endif
 
 struct DRay {
     V3 o, d;
@@ -2742,8 +2828,15 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
             V3 tl = v3(L->pos[0] - hit.p.x, L->pos[1] - hit.p.y, L->pos[2] - hit.p.z);
             real d2 = dot3(tl, tl);
             if (d2 <= RV(0.01)) d2 = RV(0.01);
+#if RT_FUSED_NORM
+            // (lanes with nothing to shade hold no hit point: they do not vote)
+            const N3 dw = sqrt_div3(tl.x, tl.y, tl.z, d2, valid);
+            const real dist = dw.L;
+            const auto wq = dw.q;
+#else
             const real dist = sqrt_r(d2);
             const auto wq = div3(tl.x, tl.y, tl.z, dist);
+#endif
             const V3 wi = v3(wq.x, wq.y, wq.z);
             if (li - l0 < kLightCache) {
                 double* c = lc + (li - l0) * 4 * 64;
@@ -2805,8 +2898,14 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
                 V3 tl = v3(L->pos[0] - hit.p.x, L->pos[1] - hit.p.y, L->pos[2] - hit.p.z);
                 real d2 = dot3(tl, tl);
                 if (d2 <= RV(0.01)) d2 = RV(0.01);
+#if RT_FUSED_NORM
+                const N3 dw = sqrt_div3(tl.x, tl.y, tl.z, d2);
+                dist = dw.L;
+                const auto wq = dw.q;
+#else
                 dist = sqrt_r(d2);
                 const auto wq = div3(tl.x, tl.y, tl.z, dist);
+#endif
                 wi = v3(wq.x, wq.y, wq.z);
             }
             const real ndotl = cmax(RV(0.0), dot3(n, wi));   // (> 0: a lit light)

@@ -152,7 +152,16 @@ __device__ __forceinline__ void std_body(const DevScene& S, const StdParams& P) 
     }
     if (active && s == 0) {
         const real inv = RV(1.0) / (real)8;
-        double* o = P.fb + ((size_t)ri * P.W + x) * 3;
+        // the pixel's row and column again, from a thread id the compiler
+        // cannot match with the one above: otherwise both stay in registers
+        // across the whole trace (the lean kernels sit at their 128-VGPR cap,
+        // and the row index was the value that went to scratch)
+        unsigned t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        const int wave2 = t >> 6, pix2 = (t & 63) >> 3;
+        const int x2 = blockIdx.x * kStdBlockX + (wave2 & 1) * kStdTW + (pix2 % kStdTW);
+        const int ri2 = blockIdx.y * kStdBlockY + (wave2 >> 1) * kStdTH + (pix2 / kStdTW);
+        double* o = P.fb + ((size_t)ri2 * P.W + x2) * 3;
         o[0] = acc.x * inv;
         o[1] = acc.y * inv;
         o[2] = acc.z * inv;

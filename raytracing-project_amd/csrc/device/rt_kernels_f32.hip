@@ -4,6 +4,8 @@
 // type of the scene records and the trace differs.
 #define RT_REAL float
 #define RT_NS rtf
+#undef RT_FUSED_NORM
+#define RT_FUSED_NORM 0   // (the fused sqrt + division is FP64 arithmetic: float keeps sqrt_r + div3)
 #define RT_NO_PLAIN   // (no plain kernel variants in the FP32 diagnostic build)
 #define RT_NO_PAPER_CODES   // (paper codes are FP64 frames only: no CODES finish kernels)
 #include "rt_device.hpp"

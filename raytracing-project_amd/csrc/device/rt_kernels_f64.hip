@@ -27,7 +27,82 @@ __global__ void k_test_pow_spec(const double* x, const double* y, int n, double*
     if (i >= n) return;
     out[i] = rtd::pow_spec(x[i], y[i]);
 }
+// norm3 / normalized (rt_device.hpp) next to __builtin_sqrt and `/` on the
+// same vectors; fast[i]: lane i's wave took the fused path.
+__global__ void k_test_norm3(const double* v, int n, double* oL, double* oq, double* pL, double* pq, int* fast,
+                             double* onrm) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const rtd::V3 a = rtd::v3(v[3 * i], v[3 * i + 1], v[3 * i + 2]);
+    const rtd::N3 r = rtd::norm3(a);
+    oL[i] = r.L;
+    oq[3 * i] = r.q.x;
+    oq[3 * i + 1] = r.q.y;
+    oq[3 * i + 2] = r.q.z;
+    fast[i] = r.fast ? 1 : 0;
+    const double L = __builtin_sqrt(rtd::dot3(a, a));
+    pL[i] = L;
+    pq[3 * i] = a.x / L;
+    pq[3 * i + 1] = a.y / L;
+    pq[3 * i + 2] = a.z / L;
+    if (onrm) {
+        const rtd::V3 u = rtd::normalized(a);
+        onrm[3 * i] = u.x;
+        onrm[3 * i + 1] = u.y;
+        onrm[3 * i + 2] = u.z;
+    }
+}
 }  // namespace
+
+static int test_norm3(const double* v_host, int n, double* L_host, double* q_host, double* plainL_host,
+                      double* plainq_host, int* fast_host, double* nrm_host) {
+    if (n <= 0 || !v_host || !L_host || !q_host || !plainL_host || !plainq_host || !fast_host) return RT_ERR_INVALID_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RT_ERR_NO_DEVICE;
+    const size_t n1 = (size_t)n * sizeof(double), n3 = 3 * n1, nf = (size_t)n * sizeof(int);
+    double *v = nullptr, *oL = nullptr, *oq = nullptr, *pL = nullptr, *pq = nullptr, *on = nullptr;
+    int* fast = nullptr;
+    int rc = RT_OK;
+    if (hipMalloc(&v, n3) != hipSuccess || hipMalloc(&oL, n1) != hipSuccess || hipMalloc(&oq, n3) != hipSuccess ||
+        hipMalloc(&pL, n1) != hipSuccess || hipMalloc(&pq, n3) != hipSuccess || hipMalloc(&fast, nf) != hipSuccess ||
+        (nrm_host && hipMalloc(&on, n3) != hipSuccess))
+        rc = RT_ERR_HIP;
+    if (rc == RT_OK && hipMemcpy(v, v_host, n3, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_HIP;
+    if (rc == RT_OK) {
+        hipLaunchKernelGGL(k_test_norm3, dim3((n + 255) / 256), dim3(256), 0, nullptr, v, n, oL, oq, pL, pq, fast, on);
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(L_host, oL, n1, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(q_host, oq, n3, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(plainL_host, pL, n1, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(plainq_host, pq, n3, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(fast_host, fast, nf, hipMemcpyDeviceToHost) != hipSuccess ||
+            (nrm_host && hipMemcpy(nrm_host, on, n3, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = RT_ERR_HIP;
+    }
+    if (v) (void)hipFree(v);
+    if (oL) (void)hipFree(oL);
+    if (oq) (void)hipFree(oq);
+    if (pL) (void)hipFree(pL);
+    if (pq) (void)hipFree(pq);
+    if (fast) (void)hipFree(fast);
+    if (on) (void)hipFree(on);
+    return rc;
+}
+
+extern "C" int rt_test_norm3(const double* v_host, int n, double* L_host, double* q_host, double* plainL_host,
+                             double* plainq_host, int* fast_host) {
+    return test_norm3(v_host, n, L_host, q_host, plainL_host, plainq_host, fast_host, nullptr);
+}
+
+extern "C" int rt_test_normalized(const double* v_host, int n, double* out_host) {
+    if (n <= 0 || !v_host || !out_host) return RT_ERR_INVALID_ARG;
+    // (the other outputs of the kernel go to scratch arrays)
+    double* tmp = new double[(size_t)n * 8];
+    int* fast = new int[n];
+    const int rc = test_norm3(v_host, n, tmp, tmp + n, tmp + 4 * (size_t)n, tmp + 5 * (size_t)n, fast, out_host);
+    delete[] tmp;
+    delete[] fast;
+    return rc;
+}
 
 extern "C" int rt_test_pow_spec(const double* x_host, const double* y_host, int n, double* out_host) {
     if (n <= 0 || !x_host || !y_host || !out_host) return RT_ERR_INVALID_ARG;

@@ -5,7 +5,7 @@
 // (rtamd::note_launch), the frame planners of csrc/host/frame_plan.hpp and the
 // jitter cache's logic over host memory (csrc/host/jitter_cache.hpp).  (The
 // distributed-frame hooks live with their transport in rt_dist.hip, rt_test_div3
-// with the FP64 kernels, the jitter cache's counts and budget with the
+// and rt_test_norm3 with the FP64 kernels, the jitter cache's counts and budget with the
 // workspaces in rt_render.hip.)
 #include <hip/hip_runtime.h>
 
