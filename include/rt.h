@@ -29,6 +29,8 @@
  *                               raytracer/src/scene.cpp:33-42
  *   rt_query_radiance        <- Tracer::trace, a batch of rays
  *                               raytracer/src/tracer.cpp:12-73
+ *   rt_query_shade           <- shade_lambert_phong, a batch of hits
+ *                               raytracer/src/shading.cpp:31-138
  *   rt_framebuffer_to_rgb8   <- framebuffer_to_mat_bgr8 / toByte
  *                               raytracer/src/main.cpp:19-34, core.h:313-316
  *   rt_write_png             <- cv::imwrite (main.cpp:86-89)
@@ -64,7 +66,8 @@ extern "C" {
                               (still 6: the batched ray queries rt_query_intersect /
                                rt_query_occluded and their *_device forms, rt_ray and
                                rt_hit, are pure additions, as are the radiance queries
-                               rt_query_radiance / rt_query_radiance_device) */
+                               rt_query_radiance / rt_query_radiance_device and the
+                               shading queries rt_query_shade / rt_query_shade_device) */
 
 /* ---------------------------------------------------------------- errors */
 enum rt_status {
@@ -459,6 +462,57 @@ int rt_query_radiance(const rt_scene* s, const rt_ray* rays_host, size_t n, int 
  * hip_stream (NULL = the default stream); blocks until done. */
 int rt_query_radiance_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, double* rgb_dev,
                              void* hip_stream, rt_stats* stats);
+
+/* --------------------------------------------------- shading queries
+ * shade_lambert_phong(scene, hit, wo) (shading.h, shading.cpp:31-138) for a
+ * batch of caller-given surface points: ambient, then every directional light,
+ * then every point light with its shadow ray, combined and clamped as in the
+ * reference.  This is the seam for light baking (a lightmap texel or a probe
+ * is a point with a normal, not a ray), for deferred shading of a G-buffer
+ * (rt_query_intersect once, then shade its hits) and for relighting the same
+ * hits under other point lights without a new scene.  For wo = -d it is
+ * Tracer::trace at recursion depth 1.
+ *
+ * rgb[3i .. 3i+2] = shade_lambert_phong(scene, Hit{t, p, n, mat of hits[i]},
+ * wo[3i .. 3i+2]).  Of an rt_hit, t, p, n and mat are read (t sets the shadow
+ * epsilon max(1e-3, 1e-4 t)); front_face is NOT READ.  n and wo are used as
+ * given, not normalised, as in the reference.  wo is required.
+ * Material index: mat == -1 gives magenta (1, 0, 1) (shading.cpp:33) without
+ * a Scene::occluded call; any other mat outside [0, n_materials) is shaded as
+ * a null material too and no table is read, in the host and device forms
+ * alike: a garbage index never reads out of bounds.
+ * hit_mask (may be NULL: every entry is shaded): where hit_mask[i] == 0,
+ * nothing of hits[i] or wo[i] is interpreted, no occlusion query is made and
+ * rgb[i] is miss_rgb, or the scene's background when miss_rgb is NULL; so
+ * rt_query_intersect's (hits, hit_mask) output is a valid input as it is.
+ * Light override: n_lights < 0: the scene's own point lights (lights is
+ * ignored); n_lights == 0: no point lights (ambient and directional lights
+ * only); n_lights > 0: these point lights instead of the scene's, for this
+ * call only (lights == NULL is RT_ERR_INVALID_ARG).  Directional lights, the
+ * ambient term and the materials are always the scene's.  lights and miss_rgb
+ * are HOST memory in both forms.  The override leaves the device's resident
+ * scene alone: a frame or query of s after it uploads nothing and renders as
+ * before.
+ * Per entry 89 B cross to the device (64 B hit, 24 B wo, 1 B mask) and 24 B
+ * back, in chunks of bounded size.  flags: RT_FLAG_NONE or RT_FLAG_NO_CULL
+ * (byte-identical results; RT_FLAG_NO_BVH / RT_FLAG_FORCE_BVH have no effect);
+ * RT_FLAG_FP32 and RT_FLAG_COUNT_OPS are RT_ERR_UNSUPPORTED, as is a scene
+ * beyond the device stacks (the frames' own limit and message).  n == 0 is
+ * RT_OK without a launch, whatever the pointers (the flags are still checked).
+ * stats (may be NULL): rays_occluded = the Scene::occluded calls the batch
+ * makes, by the reference's definition; rays_intersect 0; rays_traced =
+ * rays_occluded; pixels 0, n_gpus 1, ms_kernel, ms_total.  Uses the current HIP
+ * device and shares its resident scene copy with the frames and the other
+ * queries; waits for an open frame of the device; blocks until done. */
+int rt_query_shade(const rt_scene* s, const rt_hit* hits_host, const double* wo_host, const uint8_t* hit_mask_host,
+                   size_t n, const rt_light* lights, int n_lights, const double* miss_rgb, int flags,
+                   double* rgb_host, rt_stats* stats);
+/* The same with hits, wo, mask and colours already on the device (e.g.
+ * rt_query_intersect_device's output, in place), enqueued on hip_stream (NULL
+ * = the default stream); blocks until done. */
+int rt_query_shade_device(const rt_scene* s, const rt_hit* hits_dev, const double* wo_dev, const uint8_t* hit_mask_dev,
+                          size_t n, const rt_light* lights, int n_lights, const double* miss_rgb, int flags,
+                          double* rgb_dev, void* hip_stream, rt_stats* stats);
 
 /* ------------------------------------------------------------ host I/O */
 /* toByte(v) = round(clamp01(v)*255) (core.h:316), RGB order. */

@@ -71,12 +71,19 @@ int rt_test_radiance_kernel_name(const struct rt_scene* s, int flags, char* out,
  * RT_OK, or RT_ERR_INVALID_ARG past the end or for another table.  Host only. */
 int rt_test_radiance_kernel_row(int table, int index, char* out, int cap);
 
+/* The same pair for a shading query (rt_query_shade; e.g. "rtd::k_shade<false,
+ * false, true>"): frame_plan.hpp pick_shade_variant looked up in the shade
+ * table, and row `index` of shade launch table `table` (0 rtd, 1 rtdb).  Host
+ * only. */
+int rt_test_shade_kernel_name(const struct rt_scene* s, int flags, char* out, int cap);
+int rt_test_shade_kernel_row(int table, int index, char* out, int cap);
+
 /* The launch log: which kernels ran.  rt_test_kernel_name above is the plan
  * for a frame whose wave BVH is on and untimed; the frame itself may drop the
  * BVH (its trial frames) or launch the timed build of a paper kernel (the
  * first frame of a scene and shape).  The log records what the launchers of
- * rt_kernels.hpp / rt_query_kernels.hpp / rt_radiance_kernels.hpp were asked
- * for, host side only.
+ * rt_kernels.hpp / rt_query_kernels.hpp / rt_radiance_kernels.hpp /
+ * rt_shade_kernels.hpp were asked for, host side only.
  * on != 0: clear the log and start recording; 0: stop.  Process-wide,
  * thread-safe; while recording is off a launch pays one relaxed atomic load. */
 int rt_test_launch_log(int on);

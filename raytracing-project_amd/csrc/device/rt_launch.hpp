@@ -145,6 +145,22 @@ struct RadianceParams {
     unsigned long long* counters;
 };
 
+// A batch of shading queries (rt_query_shade): entry i of hits[0, n) / wo[3i ..
+// 3i + 2] is lane i % 64 of wave i / 64, rgb[3i .. 3i + 2] its colour
+// (shade_lambert_phong).  mask (may be null): entries with mask[i] == 0 are not
+// read and get `miss`.  The call's point lights are SceneView::lights /
+// n_lights of the launch.  counters: the frames' slots (word 1: the
+// Scene::occluded calls).
+struct ShadeParams {
+    const rt_hit* hits;
+    const double* wo;
+    const uint8_t* mask;
+    size_t n;
+    double* rgb;
+    double miss[3];
+    unsigned long long* counters;
+};
+
 // Paper mode's output alphabet (tracer.cpp:258-281): every pixel is grey
 // (r = g = b) and a function of the edge strength - the max of the constants
 // {0.9, 0.6, 0.5, 0.3} over the neighbour tests, or 0, halved when a
@@ -191,8 +207,9 @@ void note_launch(const char* ns, const char* name);
 // ray-query kernels (rt_query_kernels.hpp, their own translation units; rtf
 // has none).  launch_radiance / radiance_kernel: the radiance-query kernels
 // (rt_radiance_kernels.hpp, likewise; rtd and rtdb only, rtf defines none).
-// *_row_name(i): row i of the namespace's table, nullptr past its end
-// (rt_test_kernel_row, rt_test_radiance_kernel_row).
+// launch_shade / shade_kernel: the shading-query kernels (rt_shade_kernels.hpp,
+// likewise).  *_row_name(i): row i of the namespace's table, nullptr past its
+// end (rt_test_kernel_row, rt_test_radiance_kernel_row, rt_test_shade_kernel_row).
 #define RT_DECLARE_LAUNCHERS(NS)                                                                                  \
     namespace NS {                                                                                                \
     hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,               \
@@ -215,6 +232,10 @@ void note_launch(const char* ns, const char* name);
                                const rtamd::RadianceParams& P);                                                   \
     rtamd::KernelEntry radiance_kernel(const rtamd::KernelVariant& v);                                            \
     const char* radiance_row_name(int i);                                                                         \
+    hipError_t launch_shade(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,             \
+                            const rtamd::ShadeParams& P);                                                         \
+    rtamd::KernelEntry shade_kernel(const rtamd::KernelVariant& v);                                               \
+    const char* shade_row_name(int i);                                                                            \
     }
 RT_DECLARE_LAUNCHERS(rtd)
 RT_DECLARE_LAUNCHERS(rtf)
@@ -261,6 +282,16 @@ inline hipError_t launch_radiance(const KernelVariant& v, hipStream_t st, const 
 inline KernelEntry radiance_kernel(const KernelVariant& v) {
     return v.ns == KernelVariant::kRtf ? KernelEntry{nullptr, nullptr}
                                        : v.ns == KernelVariant::kRtdb ? rtdb::radiance_kernel(v) : rtd::radiance_kernel(v);
+}
+// (pick_shade_variant never picks rtf: no FP32 shading queries)
+inline hipError_t launch_shade(const KernelVariant& v, hipStream_t st, const SceneView& V, const ShadeParams& P) {
+    return v.ns == KernelVariant::kRtf ? hipErrorInvalidDeviceFunction
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_shade(v, st, V, P)
+                                                                      : rtd::launch_shade(v, st, V, P);
+}
+inline KernelEntry shade_kernel(const KernelVariant& v) {
+    return v.ns == KernelVariant::kRtf ? KernelEntry{nullptr, nullptr}
+                                       : v.ns == KernelVariant::kRtdb ? rtdb::shade_kernel(v) : rtd::shade_kernel(v);
 }
 inline int trace_block_threads(const KernelVariant& v, bool paper) {
     return v.ns == KernelVariant::kRtf ? rtf::kernel_block_threads(paper)

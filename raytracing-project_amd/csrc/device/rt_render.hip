@@ -19,6 +19,8 @@
 // Radiance queries (rt_query_radiance, Tracer::trace for caller-given rays,
 // tracer.cpp:12-73): the same query_impl, with the frames' ray counters;
 // kernels in rt_radiance_kernels.hpp.
+// Shading queries (rt_query_shade, shade_lambert_phong for caller-given hits,
+// shading.cpp:31-138): shade_impl next to it; kernels in rt_shade_kernels.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -51,6 +53,7 @@ using rtamd::PaperParams;
 using rtamd::QueryParams;
 using rtamd::RadianceParams;
 using rtamd::SceneView;
+using rtamd::ShadeParams;
 using rtamd::StdParams;
 
 namespace {
@@ -178,6 +181,8 @@ struct Workspace {
     DBuf ckpt, jscratch, counters;
     DBuf paper_i, paper_d, paper_aux, fb;
     DBuf q_rays, q_hits, q_mask, q_rgb;       // ray queries from host memory: one chunk's rays / hits / flags / colours
+    DBuf q_wo;                                // shading queries from host memory: one chunk's view directions
+    DBuf q_lights;                            // a shading query's own point lights (never the resident scene's `lights`)
     rtamd::JitterTable jtab;                  // mt19937(12345) checkpoint table (resident)
     rtamd::JitterJob jjob;
     rtamd::PinnedArena up;                    // page-locked staging of a frame's uploads (pinned.hpp)
@@ -986,6 +991,133 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
     return RT_OK;
 }
 
+// rt_query_shade[_device]: shade_lambert_phong of n caller-given hits.  host:
+// hits / wo / mask / rgb are host memory, moved through the workspace's chunk
+// buffers; else device memory, shaded in place on st.  lights / miss_rgb are
+// host memory in both forms.  n_lights >= 0: the call's own point lights, in a
+// workspace buffer of their own (uploaded through the page-locked arena);
+// only this call's SceneView points there, so the resident scene (ws.lights,
+// the scene cache) is what it was.  Holds the workspace lock like a frame,
+// and returns with st drained.  The Scene::occluded calls are counted in the
+// frames' counter slots: zeroed before the first launch, reduced after the last.
+int shade_impl(const char* what, const rt_scene* s, const rt_hit* hits, const double* wo, const uint8_t* mask, size_t n,
+               const rt_light* lights, int n_lights, const double* miss_rgb, int flags, double* rgb, bool host,
+               hipStream_t st, rt_stats* stats) {
+    const auto t_start = SClock::now();
+    const auto fail = [what](const char* msg, int rc) {
+        rtamd::set_last_error(std::string(what) + ": " + msg);
+        return rc;
+    };
+    if (!s) return fail("scene is NULL", RT_ERR_INVALID_ARG);
+    if (flags & ~(RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH))
+        return fail("unknown flag bits", RT_ERR_INVALID_ARG);
+    {
+        const int rv = rtamd::check_query_flags(flags);
+        if (rv != RT_OK) return rv;
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->n_gpus = 1;
+    }
+    if (n == 0) return RT_OK;
+    if (!hits) return fail("hits is NULL", RT_ERR_INVALID_ARG);
+    if (!wo) return fail("wo is NULL", RT_ERR_INVALID_ARG);
+    if (!rgb) return fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
+    if (n_lights > 0 && !lights) return fail("lights is NULL with n_lights > 0", RT_ERR_INVALID_ARG);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
+    const rt_scene_desc& d = *rt_scene_get_desc(s);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    Workspace& ws = workspace(dev);
+    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
+    // (as query_impl: nothing of this call stays queued on st when the lock goes)
+    struct Drain {
+        hipStream_t st;
+        ~Drain() { (void)hipStreamSynchronize(st); }
+    } drain{st};
+    ws.up.reset();   // (the previous frame's or query's uploads completed)
+    {
+        const int rv = scene_resident(ws, s, d, false, st);
+        if (rv != RT_OK) return rv;
+    }
+    rtamd::KernelVariant kv;
+    {
+        const int rv = rtamd::pick_shade_variant(ws.sc.cs, d, flags, &kv);
+        if (rv != RT_OK) return rv;
+    }
+    SceneView S;
+    scene_view(ws, d, flags, false, S);
+    S.n_chunks = 0;   // (the flat object list)
+    if (n_lights >= 0) {
+        // this call's point lights: k_shade (WV = 0) reads nothing else by light number
+        HIP_TRY(ws.q_lights.ensure(n_lights ? (size_t)n_lights * sizeof(rt_light) : 16));
+        HIP_TRY(rtamd::upload_async(&ws.up, ws.q_lights.p, lights, (size_t)n_lights * sizeof(rt_light), st));
+        S.lights = ws.q_lights.p;
+        S.n_lights = n_lights;
+    }
+    if (!ws.ev[0]) {
+        rtamd::SetupTimer tm(rtamd::kSetupStreams);
+        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
+    }
+    {
+        int rv = counters_ready(ws, st);
+        if (rv == RT_OK) rv = ensure_ctr_host(ws, kCounterWords);
+        if (rv != RT_OK) return rv;
+    }
+    const size_t chunk = host ? std::min(n, kQueryChunkRays) : n;
+    if (host) {
+        HIP_TRY(ws.q_hits.ensure(chunk * sizeof(rt_hit)));
+        HIP_TRY(ws.q_wo.ensure(chunk * 3 * sizeof(double)));
+        if (mask) HIP_TRY(ws.q_mask.ensure(chunk));
+        HIP_TRY(ws.q_rgb.ensure(chunk * 3 * sizeof(double)));
+    }
+    double ms_kernel = 0.0;
+    for (size_t c0 = 0; c0 < n; c0 += chunk) {
+        const size_t cn = std::min(chunk, n - c0);
+        const rt_hit* d_hits = host ? ws.q_hits.as<rt_hit>() : hits + c0;
+        const double* d_wo = host ? ws.q_wo.as<double>() : wo + 3 * c0;
+        const uint8_t* d_mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask + c0;
+        double* d_rgb = host ? ws.q_rgb.as<double>() : rgb + 3 * c0;
+        if (host) {
+            HIP_TRY(hipMemcpyAsync(ws.q_hits.p, hits + c0, cn * sizeof(rt_hit), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ws.q_wo.p, wo + 3 * c0, cn * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+            if (mask) HIP_TRY(hipMemcpyAsync(ws.q_mask.p, mask + c0, cn, hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(hipEventRecord(ws.ev[1], st));
+        for (size_t l0 = 0; l0 < cn; l0 += kQueryLaunchRays) {
+            ShadeParams P;
+            P.n = std::min(kQueryLaunchRays, cn - l0);
+            P.hits = d_hits + l0;
+            P.wo = d_wo + 3 * l0;
+            P.mask = d_mask ? d_mask + l0 : nullptr;
+            P.rgb = d_rgb + 3 * l0;
+            for (int c = 0; c < 3; ++c) P.miss[c] = miss_rgb ? miss_rgb[c] : d.background[c];
+            P.counters = ws.counters.as<unsigned long long>();
+            HIP_TRY(rtamd::launch_shade(kv, st, S, P));
+        }
+        HIP_TRY(hipEventRecord(ws.ev[2], st));
+        if (host) HIP_TRY(hipMemcpyAsync(rgb + 3 * c0, d_rgb, cn * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        // (the chunk buffers and the events are reused by the next chunk)
+        HIP_TRY(hipStreamSynchronize(st));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) ms_kernel += ms;
+    }
+    // the slots' sums, as a frame's end reads them (and the slots are left zero)
+    hipLaunchKernelGGL(k_reduce_counters, dim3(kCounterWords), dim3(64), 0, st, ws.counters.as<unsigned long long>(),
+                       ws.ctr_host, nullptr, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    ws.counters_zero = true;
+    if (stats) {
+        stats->rays_occluded = ((volatile unsigned long long*)ws.ctr_host)[1];
+        stats->rays_traced = stats->rays_occluded;
+        stats->ms_kernel = ms_kernel;
+        stats->ms_total = ms_since(t_start);
+    }
+    return RT_OK;
+}
+
 }  // namespace
 
 void rtamd::set_workspace_slot(int slot) { t_ws_slot = slot; }
@@ -1090,7 +1222,7 @@ int rtamd::release_device_workspaces(int min_slot) {
                         &w->wobjs, &w->wctab, &w->worig, &w->wchunk,
                         &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->ckpt,
                         &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime,
-                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb})
+                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb, &w->q_wo, &w->q_lights})
             b->release();
         w->jtab.release();
         w->jcache.release();   // every cached entry and the uncached buffer (the hit / miss counts stay)
@@ -1332,6 +1464,21 @@ extern "C" int rt_query_radiance_device(const rt_scene* s, const rt_ray* rays_de
                                         void* hip_stream, rt_stats* stats) {
     return query_impl("rt_query_radiance_device", s, rtamd::kQueryRadiance, rays_dev, n, flags, nullptr, nullptr, rgb_dev,
                       false, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_query_shade(const rt_scene* s, const rt_hit* hits_host, const double* wo_host,
+                              const uint8_t* hit_mask_host, size_t n, const rt_light* lights, int n_lights,
+                              const double* miss_rgb, int flags, double* rgb_host, rt_stats* stats) {
+    return shade_impl("rt_query_shade", s, hits_host, wo_host, hit_mask_host, n, lights, n_lights, miss_rgb, flags,
+                      rgb_host, true, nullptr, stats);
+}
+
+extern "C" int rt_query_shade_device(const rt_scene* s, const rt_hit* hits_dev, const double* wo_dev,
+                                     const uint8_t* hit_mask_dev, size_t n, const rt_light* lights, int n_lights,
+                                     const double* miss_rgb, int flags, double* rgb_dev, void* hip_stream,
+                                     rt_stats* stats) {
+    return shade_impl("rt_query_shade_device", s, hits_dev, wo_dev, hit_mask_dev, n, lights, n_lights, miss_rgb, flags,
+                      rgb_dev, false, (hipStream_t)hip_stream, stats);
 }
 
 extern "C" int rt_scatter_rows_device(const double* src_dev, const int32_t* rows_dev, int n_rows, int W,

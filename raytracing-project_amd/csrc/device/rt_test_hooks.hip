@@ -46,7 +46,7 @@ int scene_variant(const rt_scene* s, int mode, int flags, rtamd::KernelVariant* 
 }  // namespace
 
 // ------------------------------------------------------------- launch log
-// note_launch is called by every launcher (rt_kernels.hpp, rt_query_kernels.hpp, rt_radiance_kernels.hpp)
+// note_launch is called by every launcher (rt_kernels.hpp, rt_query_kernels.hpp, rt_radiance_kernels.hpp, rt_shade_kernels.hpp)
 // right before its hipLaunchKernelGGL; off, it is one relaxed load.
 namespace {
 std::atomic<int> g_log_on{0};
@@ -252,6 +252,31 @@ extern "C" int rt_test_radiance_kernel_name(const rt_scene* s, int flags, char* 
 extern "C" int rt_test_radiance_kernel_row(int table, int index, char* out, int cap) {
     if (!out || cap <= 0 || index < 0 || (table != 0 && table != 1)) return RT_ERR_INVALID_ARG;
     const char* name = table ? rtdb::radiance_row_name(index) : rtd::radiance_row_name(index);
+    if (!name) return RT_ERR_INVALID_ARG;
+    std::snprintf(out, (size_t)cap, "%s::%s", table ? "rtdb" : "rtd", name);
+    return RT_OK;
+}
+
+extern "C" int rt_test_shade_kernel_name(const rt_scene* s, int flags, char* out, int cap) {
+    if (!s || !out || cap <= 0) return RT_ERR_INVALID_ARG;
+    rtamd::KernelVariant v;
+    try {
+        const rt_scene_desc& d = *rt_scene_get_desc(s);
+        const int rc = rtamd::pick_shade_variant(rtamd::compile_scene(d), d, flags, &v);
+        if (rc != RT_OK) return rc;
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("scene compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+    const rtamd::KernelEntry k = rtamd::shade_kernel(v);
+    if (!k.name) { rtamd::set_last_error("rt_test_shade_kernel_name: no kernel for this variant"); return RT_ERR_UNSUPPORTED; }
+    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
+    return RT_OK;
+}
+
+extern "C" int rt_test_shade_kernel_row(int table, int index, char* out, int cap) {
+    if (!out || cap <= 0 || index < 0 || (table != 0 && table != 1)) return RT_ERR_INVALID_ARG;
+    const char* name = table ? rtdb::shade_row_name(index) : rtd::shade_row_name(index);
     if (!name) return RT_ERR_INVALID_ARG;
     std::snprintf(out, (size_t)cap, "%s::%s", table ? "rtdb" : "rtd", name);
     return RT_OK;

@@ -132,6 +132,11 @@ int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flag
     return RT_OK;
 }
 
+int pick_shade_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out) {
+    // (shade()'s only scene walk is Scene::occluded: the occluded query's rule)
+    return pick_query_variant(cs, d, flags, out);
+}
+
 int pick_radiance_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out) {
     int rc = check_query_flags(flags);
     if (rc != RT_OK) return rc;

@@ -71,6 +71,14 @@ int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int 
 int check_query_flags(int flags);
 int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
 
+// The variant a shading query (rt_query_shade: shade_lambert_phong of
+// caller-given hits) of (scene, flags) launches: pick_query_variant's rule, as
+// the kernel's scene walks are the shadow rays' Scene::occluded calls (E, D,
+// PL and the stack tier of a query without recursion frames; D also carries
+// the directional lights' code).  Looked up in the shade tables (rt_launch.hpp
+// shade_kernel).
+int pick_shade_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
+
 // The variant a radiance query (rt_query_radiance: Tracer::trace of caller-given
 // rays) of (scene, flags) launches: check_query_flags first, then
 // pick_variant's standard-mode rules with per-lane culls forced (wv = 0, as

@@ -200,6 +200,14 @@ def amd_lib():
                                                      C.c_void_p, C.POINTER(Stats)]
             lib.rt_test_radiance_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
             lib.rt_test_radiance_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
+        if hasattr(lib, "rt_query_shade"):   # (likewise)
+            lib.rt_query_shade.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Stats)]
+            lib.rt_query_shade_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(Stats)]
+            lib.rt_test_shade_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+            lib.rt_test_shade_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
         lib.rt_device_count.restype = C.c_int
         lib.rt_render_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                         C.POINTER(Stats)]
@@ -410,6 +418,24 @@ def with_dir_lights(scene: Scene, lights) -> Scene:
         arr[i].radiance[:] = [float(v) for v in rad]
     d.n_dir_lights = len(lights)
     d.dir_lights = C.cast(arr, C.POINTER(DirLight))
+    return scene_from_desc(d)
+
+
+def with_point_lights(scene: Scene, lights) -> Scene:
+    """Copy of `scene` whose point lights are [(pos, intensity), ...] (the
+    reference's Scene::point_lights); everything else, the directional lights
+    included, is the scene's."""
+    d = SceneDesc.from_buffer_copy(scene.desc)
+    arr, d.n_lights = _light_array(lights)
+    d.lights = C.cast(arr, C.POINTER(Light))
+    return scene_from_desc(d)
+
+
+def with_recursion_limit(scene: Scene, k: int) -> Scene:
+    """Copy of `scene` with Scene::recursion_limit = k (at 1, Tracer::trace
+    returns the hit's shade_lambert_phong: tracer.cpp:36-38)."""
+    d = SceneDesc.from_buffer_copy(scene.desc)
+    d.recursion_limit = int(k)
     return scene_from_desc(d)
 
 
@@ -776,6 +802,93 @@ def radiance_rows(table: int) -> list[str]:
     return out
 
 
+def _light_array(lights):
+    """(rt_light array or None, n_lights) of a light override: None = the
+    scene's own (n_lights -1), else [(pos, intensity), ...]."""
+    if lights is None:
+        return None, -1
+    arr = (Light * max(1, len(lights)))()
+    for i, (pos, inten) in enumerate(lights):
+        arr[i].pos[:] = [float(v) for v in pos]
+        arr[i].intensity[:] = [float(v) for v in inten]
+    return arr, len(lights)
+
+
+def query_shade(scene: Scene, hits, wo, mask=None, lights=None, miss_rgb=None, flags: int = RT_FLAG_NONE,
+                stats: Stats | None = None) -> np.ndarray:
+    """rt_query_shade: shade_lambert_phong(scene, hits[i], wo[i]) of every
+    entry, as an (n, 3) float64 array.  hits: a HIT_DTYPE array (t, p, n, mat
+    are read); wo: (n, 3); mask (optional, n bytes): entries with 0 get
+    miss_rgb (None: the scene's background); lights: None = the scene's own
+    point lights, else [(pos, intensity), ...] instead of them."""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n = len(hits)
+    wo = np.ascontiguousarray(wo, dtype=np.float64)
+    if wo.shape != (n, 3):
+        raise ValueError(f"wo must be an (n, 3) array for n = {n} hits, got {wo.shape}")
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.shape != (n,):
+            raise ValueError(f"mask must hold n = {n} flags, got {m.shape}")
+    arr, nl = _light_array(lights)
+    miss = None if miss_rgb is None else (C.c_double * 3)(*[float(v) for v in miss_rgb])
+    rgb = np.zeros((n, 3), dtype=np.float64)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_shade(scene.handle, hits.ctypes.data_as(C.c_void_p), wo.ctypes.data_as(C.c_void_p),
+                                  m.ctypes.data_as(C.c_void_p) if m is not None else None, n,
+                                  C.cast(arr, C.c_void_p) if arr is not None else None, nl,
+                                  C.cast(miss, C.c_void_p) if miss is not None else None, flags,
+                                  rgb.ctypes.data_as(C.c_void_p), C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return rgb
+
+
+def query_shade_device(scene: Scene, hits_dev: DeviceBuffer, wo_dev: DeviceBuffer, mask_dev: DeviceBuffer | None,
+                       n: int, rgb_dev: DeviceBuffer, lights=None, miss_rgb=None, flags: int = RT_FLAG_NONE,
+                       stream: Stream | None = None, stats: Stats | None = None) -> None:
+    """rt_query_shade_device: the first n rt_hit records of hits_dev with the
+    first 3n doubles of wo_dev (and the first n bytes of mask_dev, when given)
+    into the first 3n doubles of rgb_dev, on `stream` (None: the default
+    stream).  lights / miss_rgb are host values, as for query_shade."""
+    if n < 0 or hits_dev.nbytes < n * HIT_DTYPE.itemsize or wo_dev.nbytes < n * 24 or rgb_dev.nbytes < n * 24 \
+            or (mask_dev is not None and mask_dev.nbytes < n):
+        raise ValueError("query_shade_device: a buffer is too small for n entries")
+    arr, nl = _light_array(lights)
+    miss = None if miss_rgb is None else (C.c_double * 3)(*[float(v) for v in miss_rgb])
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_shade_device(scene.handle, hits_dev.ptr, wo_dev.ptr,
+                                         mask_dev.ptr if mask_dev is not None else None, n,
+                                         C.cast(arr, C.c_void_p) if arr is not None else None, nl,
+                                         C.cast(miss, C.c_void_p) if miss is not None else None, flags, rgb_dev.ptr,
+                                         stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def shade_kernel_name(scene: Scene, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
+    """rt_test_shade_kernel_name: (status, "ns::kernel") of the kernel a
+    shading query of this scene and flags launches.  Host only."""
+    buf = C.create_string_buffer(160)
+    rc = amd_lib().rt_test_shade_kernel_name(scene.handle, flags, buf, 160)
+    return rc, buf.value.decode()
+
+
+SHADE_TABLES = ("rtd shade", "rtdb shade")
+
+
+def shade_rows(table: int) -> list[str]:
+    """rt_test_shade_kernel_row: the rows ("ns::kernel") of shade launch
+    table `table` (an index into SHADE_TABLES).  Host only."""
+    lib = amd_lib()
+    buf = C.create_string_buffer(160)
+    out = []
+    while lib.rt_test_shade_kernel_row(table, len(out), buf, 160) == RT_OK:
+        out.append(buf.value.decode())
+    return out
+
+
 def render_multi(scene: Scene, width: int, height: int, mode: int, n_gpus: int, flags: int = RT_FLAG_NONE,
                  stats: Stats | None = None) -> np.ndarray:
     """rt_render_multi: the frame over n_gpus devices of this process."""
@@ -961,6 +1074,93 @@ def oracle_trace_dirs(origins, dirs) -> np.ndarray:
     """The directions oracle_trace really traces: (o + d) - o in float64."""
     o = np.asarray(origins, dtype=np.float64)
     return (o + np.asarray(dirs, dtype=np.float64)) - o
+
+
+def oracle_shade(scene: Scene, hits, wo, lights=None):
+    """shade_lambert_phong(scene, hit, wo) of every hit: (rgb (n, 3),
+    n_occluded (n,)), the colour and the Scene::occluded calls of each.  TEST
+    ONLY.  A numpy restatement of shading.cpp:31-138, statement by statement
+    in float64, whose Scene::occluded is answered by oracle_occluded (the
+    pinned oracle); what oracle_trace cannot do: a wo that is not -d, a hit
+    point that is not a ray's.  hits: a HIT_DTYPE array (t, p, n, mat; a mat
+    outside [0, n_materials) is a null material: magenta, no query); lights:
+    None = the scene's point lights, else [(pos, intensity), ...] instead.
+    std::max(a, b) is a < b ? b : a and std::min(a, b) is b < a ? b : a, which
+    is what decides for a NaN; tests/test_shade_plan.py holds the restatement
+    to the oracle's own shading."""
+    hits = np.asarray(hits, dtype=HIT_DTYPE)
+    wo_all = np.asarray(wo, dtype=np.float64)
+    n_all = len(hits)
+    d = scene.desc
+    rgb = np.empty((n_all, 3))
+    rgb[:] = (1.0, 0.0, 1.0)   # shading.cpp:33
+    n_occ = np.zeros(n_all, dtype=np.int64)
+    idx = np.flatnonzero((hits["mat"] >= 0) & (hits["mat"] < d.n_materials))
+    if not len(idx):
+        return rgb, n_occ
+    mats = [d.materials[i] for i in range(d.n_materials)]
+    field = lambda f: np.array([getattr(m, f) for m in mats])[hits["mat"][idx]]   # noqa: E731
+    albedo = np.array([list(m.albedo) for m in mats])[hits["mat"][idx]]
+    ambient = np.array([list(m.ambient) for m in mats])[hits["mat"][idx]]
+    kd, ks, shin = field("kd"), field("ks"), field("shininess")
+    p, n, t, wo = hits["p"][idx], hits["n"][idx], hits["t"][idx], wo_all[idx]
+    if lights is None:
+        lights = [(list(d.lights[i].pos), list(d.lights[i].intensity)) for i in range(d.n_lights)]
+    smax = lambda a, b: np.where(a < b, b, a)   # noqa: E731  (std::max)
+    dot = lambda a, b: a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]   # noqa: E731
+
+    def normalized(v):   # core.h:95-101
+        L = np.sqrt(dot(v, v))
+        return np.where((L > 1e-6)[:, None], v / L[:, None], np.array([0.0, 1.0, 0.0]))
+
+    def combine(a, b):
+        return 1.0 - (1.0 - a) * (1.0 - b)
+
+    def occluded(need, wi, tmax):
+        occ = np.zeros(len(idx), dtype=bool)
+        k = np.flatnonzero(need)
+        if len(k):
+            occ[k] = oracle_occluded(scene, so[k], wi[k], eps[k], tmax[k])
+            n_occ[idx[k]] += 1
+        return occ
+
+    def light_term(lit, E, wi, ndotl, I, diffuse_scale):
+        E_d = albedo * I * (kd * ndotl * diffuse_scale if diffuse_scale is not None else kd * ndotl)[:, None]
+        ndw = dot(n, wi)
+        r = normalized((2.0 * ndw)[:, None] * n - wi)
+        rdotv = smax(0.0, dot(r, wo))
+        spec = np.power(rdotv, shin) * ks
+        E_s = np.where((ks > 0.0)[:, None], I * spec[:, None], 0.0)
+        return np.where(lit[:, None], combine(E, combine(E_d, E_s)), E)
+
+    with np.errstate(all="ignore"):
+        E = ambient * np.array(list(d.ambient))
+        eps = smax(1e-3, 1e-4 * t)
+        so = p + n * eps[:, None]
+        inf = np.full(len(idx), np.inf)
+        for li in range(d.n_dir_lights):
+            L = d.dir_lights[li]
+            wi = normalized(np.tile(-np.array(list(L.dir)), (len(idx), 1)))
+            ndotl = smax(0.0, dot(n, wi))
+            need = ~(ndotl <= 0.0)
+            lit = need & ~occluded(need, wi, inf)
+            E = light_term(lit, E, wi, ndotl, np.tile(np.array(list(L.radiance)), (len(idx), 1)), None)
+        for pos, inten in lights:
+            tl = np.array([float(v) for v in pos]) - p
+            d2 = dot(tl, tl)
+            d2 = np.where(d2 <= 0.01, 0.01, d2)
+            dist = np.sqrt(d2)
+            wi = tl / dist[:, None]
+            ndotl = smax(0.0, dot(n, wi))
+            max_t = dist - eps
+            need = ~(ndotl <= 0.0) & ~(max_t <= eps)
+            lit = need & ~occluded(need, wi, max_t)
+            ed = smax(0.5, dist)
+            falloff = 1.0 / (ed * ed)
+            I = np.array([float(v) for v in inten]) * (falloff * 2.0)[:, None]
+            E = light_term(lit, E, wi, ndotl, I, 1.5)
+        rgb[idx] = np.where(E < 1.5, E, 1.5)   # std::min(1.5, E)
+    return rgb, n_occ
 
 
 def oracle_primary_hits(scene: Scene) -> np.ndarray:

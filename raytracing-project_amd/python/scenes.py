@@ -1031,6 +1031,21 @@ def radiance_recipes() -> list[Recipe]:
     return out
 
 
+def shade_recipes() -> list[Recipe]:
+    """One Recipe (row, scene name, flags; mode, frame unused) per row of the
+    shade launch tables (rt_test.h rt_test_shade_kernel_row): k_shade<E, D,
+    PL>, the occluded query's columns, so the query rows' scenes fit.
+    tests/test_shade_plan.py holds this list against the tables,
+    tests/test_gpu_shade.py queries every entry."""
+    out = []
+    b = lambda v: "true" if v else "false"   # noqa: E731
+    for ns, e, d, pl, scene in (("rtd", 1, 1, 0, "query/torture/xform_in_csg"), ("rtd", 0, 1, 0, "query/dir/pokeball_csg_sun"),
+                                ("rtd", 0, 0, 0, "query/bvh/ties"), ("rtd", 0, 0, 1, "query/config3"),
+                                ("rtdb", 1, 1, 0, "query/deep/xform_nest12")):
+        out.append(Recipe(f"{ns}::k_shade<{b(e)}, {b(d)}, {b(pl)}>", scene, 0, 0, 0))
+    return out
+
+
 def row_timed(row: str, timed: bool) -> str:
     """A paper primary row's name with its T argument set (k_paper_primary<E,
     D, C[, T]>: the untimed rows leave T out; k_paper_primary_lean<C, WV, T,

@@ -38,6 +38,7 @@ static int check_file(const char* path, const char* png_out) {
             (void)rtamd::pick_variant(cs, *d, mode, flags, true, &v);   // (a refusal is a valid outcome)
             if (mode == 0) (void)rtamd::pick_query_variant(cs, *d, flags, &v);   // (the ray queries' kernel choice)
             if (mode == 0) (void)rtamd::pick_radiance_variant(cs, *d, flags, &v);   // (the radiance queries')
+            if (mode == 0) (void)rtamd::pick_shade_variant(cs, *d, flags, &v);   // (the shading queries')
         }
     int W = rt_camera_width(&d->camera), H = rt_camera_height(&d->camera);
     if (W > 64) W = 64;
