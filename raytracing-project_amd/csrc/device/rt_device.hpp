@@ -1582,13 +1582,26 @@ __device__ __forceinline__ bool plane_touch(const float4 c0, const float4 c1, co
     return !((sa > m) & (sb > m)) & !((sa < -m) & (sb < -m));
 }
 
+// shade()'s shadow rays reach the functions below as r0 = (so, wi), BEFORE
+// the Ray constructor's re-normalisation of the direction (core.h:278), and
+// the f32 culls measure the segment [tmin, tmax] along wi as if it were unit.
+// It is, to a few FP64 ulps (far inside their margins), for a `regular` lane.
+// Where the reference clamps the light distance (dist_squared <= 0.01,
+// shading.cpp:81-84) wi = to_light / 0.1 is shorter than 1 and the
+// reference's segment runs 0.1 - eps along wi / |wi|, past the light: a lane
+// that is not regular takes part in no f32 cull (no bundle is formed with it,
+// and its per-lane tests pass), so its objects get their FP64 evaluation.
+// Scenes of ordinary size meet this only where a light lies within 0.1 of a
+// surface; a scene 100 times smaller is such a place as a whole.
+
 // Scene::occluded (scene.cpp:33-42): any hit; per-lane early exit.
 // lazy: r.d is the shadow direction BEFORE the Ray constructor's
-// re-normalisation (core.h:278); the f32 culls use it as it is (a few FP64
-// ulps from the normalised one, far inside their margins) and the exact ray
-// is formed only once an object survives them (as scene_occluded_capsule).
+// re-normalisation (core.h:278); the f32 culls use it as it is for regular
+// lanes (above) and the exact ray is formed only once an object survives them
+// (as scene_occluded_capsule).
 template <bool EAGER, bool DEEP, class CT>
-__device__ bool scene_occluded(const DevScene& S, const DRay& r0, real tmin, real tmax, CT& cnt, bool lazy = false) {
+__device__ bool scene_occluded(const DevScene& S, const DRay& r0, real tmin, real tmax, CT& cnt, bool lazy = false,
+                               bool regular = true) {
     bool hit = false;
     DRay r = r0;
     bool r_exact = !lazy;
@@ -1599,7 +1612,7 @@ __device__ bool scene_occluded(const DevScene& S, const DRay& r0, real tmin, rea
         const DevObj ob = S.objs[o];
         if (ob.kind == rtamd::OBJ_NEVER) continue;
         if (ob.has_bound && S.cull) {
-            if (!__any(!hit && ball_touch(ob.fb, fr, ftmin, ftmax))) {
+            if (!__any(!hit && (!regular || ball_touch(ob.fb, fr, ftmin, ftmax)))) {
                 cnt.inc(RT_OPC_CULLED);
                 if (ob.kind == rtamd::OBJ_GROUP) o += ob.m;
                 continue;
@@ -1607,7 +1620,7 @@ __device__ bool scene_occluded(const DevScene& S, const DRay& r0, real tmin, rea
         } else if (S.cull && ob.kind != rtamd::OBJ_GROUP) {
             // a bare half-space: skipped unless some lane's segment crosses its plane
             const float4 c1 = S.ctab[2 * o + 1];
-            if (__float_as_int(c1.x) == 3 && !__any(!hit && plane_touch(S.ctab[2 * o], c1, fr, ftmin, ftmax))) {
+            if (__float_as_int(c1.x) == 3 && !__any(!hit && (!regular || plane_touch(S.ctab[2 * o], c1, fr, ftmin, ftmax)))) {
                 cnt.inc(RT_OPC_CULLED);
                 continue;
             }
@@ -1787,11 +1800,13 @@ __device__ __forceinline__ bool record_touch(const float4 c0, const float4 c1, c
 // false for lanes with need = false.
 //
 // r0 is the shadow ray BEFORE the Ray constructor's re-normalisation of its
-// direction (core.h:278): the f32 culling works on it directly (the
-// re-normalised direction differs by a few FP64 ulps, far inside every cull
-// test's 1e-5 margins), and the exact FP64 ray (make_ray, one sqrt and three
-// divisions per lane) is formed only when some candidate object survives the
-// culls and is evaluated - most shadow queries of a wave end before that.
+// direction (core.h:278): the f32 culling works on it directly for regular
+// lanes (the re-normalised direction differs by a few FP64 ulps, far inside
+// every cull test's 1e-5 margins; a lane that is not regular switches the
+// capsule off and passes its per-lane tests), and the exact FP64 ray
+// (make_ray, one sqrt and three divisions per lane) is formed only when some
+// candidate object survives the culls and is evaluated - most shadow queries
+// of a wave end before that.
 //
 // BV (wave BVH kernels): S.objs is the Morton-ordered list in chunks of 64
 // with a cull record per chunk (CompiledScene::wobjs / wchunk); one
@@ -1800,7 +1815,7 @@ __device__ __forceinline__ bool record_touch(const float4 c0, const float4 c1, c
 // an OR over objects, so the order is free.
 template <bool EAGER, bool DEEP, bool UO, bool BV = false, bool LEAD = false, class CT>
 __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real tmin, real tmax, bool need, bool wave_ok,
-                                    CT& cnt) {
+                                    CT& cnt, bool regular = true) {
 #if defined(RT_ABL) && RT_ABL == 1   // diagnostic ablation builds only (wrong images): no shadow queries
     return false;
 #endif
@@ -1819,10 +1834,10 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
                 Az = __builtin_fmaf(ftmin, fr.dz, fr.oz);
     const float Bx = __builtin_fmaf(ftmax, fr.dx, fr.ox), By = __builtin_fmaf(ftmax, fr.dy, fr.oy),
                 Bz = __builtin_fmaf(ftmax, fr.dz, fr.oz);
-    const bool fin = __builtin_isfinite(Ax + Ay + Az + Bx + By + Bz);
-    // without the capsule (a partially active wave, or unbounded / non-finite
-    // segments) every object is a candidate and each bounded one gets the
-    // per-lane segment test
+    const bool fin = __builtin_isfinite(Ax + Ay + Az + Bx + By + Bz) && regular;
+    // without the capsule (a partially active wave, unbounded / non-finite
+    // segments, or a lane whose direction is not unit) every object is a
+    // candidate and each bounded one gets the per-lane segment test
     const bool cap = wave_ok && exec_full() && !__any(need && !fin);
     const float ax = rdlane_f(Ax, f), ay = rdlane_f(Ay, f), az = rdlane_f(Az, f);
     const float bx = rdlane_f(Bx, f), by = rdlane_f(By, f), bz = rdlane_f(Bz, f);
@@ -1983,7 +1998,7 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
                 }
             }
             if (S.cull && ob.has_bound) {   // per-lane segment test (f32, cheaper than an FP64 miss)
-                if (!__any(need && !hit && ball_touch(ob.fb, fr, ftmin, ftmax))) {
+                if (!__any(need && !hit && (!regular || ball_touch(ob.fb, fr, ftmin, ftmax)))) {
                     if (need) cnt.inc(RT_OPC_CULLED);
                     cnt.pe(PH_OBJ_PREF);
                     continue;
@@ -2430,7 +2445,7 @@ __device__ bool scene_occluded_wave(const DevScene& S, const DRay& r0, real tmin
                 // lane's actual segment: its eps offset from the hit point is
                 // what clears the object a lane itself lies on
                 const FRay fr = to_fray(r0);
-                if (!__any(need && !hit && ball_touch(ob.fb, fr, (float)tmin, (float)tmax))) {
+                if (!__any(need && !hit && (!regular || ball_touch(ob.fb, fr, (float)tmin, (float)tmax)))) {
                     if (need) cnt.inc(RT_OPC_CULLED);
                     cnt.pe(PH_OBJ_PREF);
                     continue;
@@ -2827,7 +2842,8 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
             if (valid) cnt.inc(RT_OPC_LIGHT_EVAL);
             V3 tl = v3(L->pos[0] - hit.p.x, L->pos[1] - hit.p.y, L->pos[2] - hit.p.z);
             real d2 = dot3(tl, tl);
-            if (d2 <= RV(0.01)) d2 = RV(0.01);
+            const bool clamped = d2 <= RV(0.01);   // (wi = tl / 0.1 is not unit then: no f32 culls)
+            if (clamped) d2 = RV(0.01);
 #if RT_FUSED_NORM
             // (lanes with nothing to shade hold no hit point: they do not vote)
             const N3 dw = sqrt_div3(tl.x, tl.y, tl.z, d2, valid);
@@ -2858,15 +2874,16 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
                 cnt.pb(PH_SHADOW);
                 // (the direction's re-normalisation happens inside, when needed)
                 occ = scene_occluded_wave<EAGER, DEEP, UO, true>(S, DRay{so, wi}, eps, max_t, need, wave_full, cnt, li,
-                                                                 hull, d2 > RV(0.01));
+                                                                 hull, !clamped);
                 cnt.pe(PH_SHADOW);
             } else if constexpr (WV) {
                 cnt.pb(PH_SHADOW);
-                occ = scene_occluded_capsule<EAGER, DEEP, UO, false, LEAD>(S, DRay{so, wi}, eps, max_t, need, wave_full, cnt);
+                occ = scene_occluded_capsule<EAGER, DEEP, UO, false, LEAD>(S, DRay{so, wi}, eps, max_t, need, wave_full, cnt,
+                                                                           !clamped);
                 cnt.pe(PH_SHADOW);
             } else if (need) {
                 // (the direction's re-normalisation happens inside, when needed)
-                occ = scene_occluded<EAGER, DEEP>(S, DRay{so, wi}, eps, max_t, cnt, true);
+                occ = scene_occluded<EAGER, DEEP>(S, DRay{so, wi}, eps, max_t, cnt, true, !clamped);
             }
             if (need) {
                 ++n_occl;

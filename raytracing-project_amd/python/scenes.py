@@ -880,6 +880,112 @@ def deep_recursion_scene(recursion: int, dpi: int = 8) -> dict:
     return s
 
 
+# ------------------------------------------------------------ placed scenes
+# name -> (scale, offset): where the culling tests put a scene (placed()).
+# Frames stop at x24 (dpi is an integer: 24 -> 1); queries have no camera and
+# carry the large scales.  e25: the f32 squares of the coordinates overflow
+# while the coordinates are finite; e39: the f32 copies themselves are inf.
+PLACEMENTS = {
+    "mid": (1.0, (3000.7, -2000.3, 1000.1)),
+    "far": (1.0, (1e6 + 0.3, -7.5e5 - 0.7, 5e5 + 0.1)),
+    "x24": (24.0, (0.0, 0.0, 0.0)),
+    "x24_far": (24.0, (7.2e4 + 0.3, -4.8e4 - 0.7, 2.4e4 + 0.1)),
+    "d100_mid": (0.01, (30.007, -20.003, 10.001)),
+    "big": (1000.0, (0.0, 0.0, 0.0)),
+    "huge_far": (1e5, (3e8 + 0.3, -2e8, 1e8)),
+    "tiny": (1e-3, (0.0, 0.0, 0.0)),
+    "e25": (1e25, (0.0, 0.0, 0.0)),
+    "e39": (1e39, (0.0, 0.0, 0.0)),
+}
+FRAME_PLACEMENTS = ("mid", "far", "x24", "x24_far", "d100_mid")
+QUERY_PLACEMENTS = ("mid", "far", "big", "huge_far", "tiny", "e25", "e39")
+
+
+def placed(scene: dict, scale: float, offset) -> dict:
+    """The JSON scene under the similarity x -> scale * x + offset, as a deep
+    copy: positions mapped, lengths (radii, translation factors, the screen's
+    dimensions) x scale, dpi / scale (an integer >= 1, so that a frame keeps
+    its W x H; ValueError otherwise), light intensities x scale^2 (the falloff
+    is 1 / d^2).  Normals, angles, button directions, materials, the medium
+    and the background stay.  scaling and rotation nodes act about the origin
+    and do not commute with an offset: with a non-zero offset they become
+    translation(+offset) o node o translation(-offset) o placed subject.  A
+    key this function does not know raises KeyError."""
+    scale = float(scale)
+    off = [float(v) for v in offset]
+    if len(off) != 3:
+        raise ValueError("offset must have three components")
+    moved = any(v != 0.0 for v in off)
+
+    def point(p):
+        return [scale * float(p[i]) + off[i] for i in range(3)]
+
+    def node(nd):
+        (kind, body), = nd.items()
+        if kind in ("union", "intersection", "difference"):
+            return {kind: [node(c) for c in body]}
+        out = copy.deepcopy(body)
+        if kind == "sphere":
+            _known(body, ("position", "radius", "color", "index"), kind)
+            out["position"], out["radius"] = point(body["position"]), scale * body["radius"]
+        elif kind == "pokeball":
+            _known(body, ("position", "radius", "button_dir", "belt_half", "button_outer", "ring_width", "colors"),
+                   kind)
+            out["position"], out["radius"] = point(body["position"]), scale * body["radius"]
+        elif kind == "halfSpace":
+            _known(body, ("position", "normal", "color", "index"), kind)
+            out["position"] = point(body["position"])
+        elif kind == "translation":
+            _known(body, ("factors", "subject"), kind)
+            out["factors"] = [scale * float(v) for v in body["factors"]]
+            out["subject"] = node(body["subject"])
+        elif kind in ("scaling", "rotation"):
+            _known(body, ("factors", "subject") if kind == "scaling" else ("angle", "direction", "subject"), kind)
+            out["subject"] = node(body["subject"])
+            if moved:
+                out["subject"] = {"translation": {"factors": [-v for v in off], "subject": out["subject"]}}
+                return {"translation": {"factors": list(off), "subject": {kind: out}}}
+        elif kind == "csg":
+            _known(body, ("operator", "left", "right"), kind)
+            out["left"], out["right"] = node(body["left"]), node(body["right"])
+        else:
+            raise KeyError(kind)
+        return {kind: out}
+
+    s = {}
+    for key, val in scene.items():
+        if key == "screen":
+            _known(val, ("dpi", "dimensions", "position", "observer"), key)
+            scr = copy.deepcopy(val)
+            dpi = val["dpi"] / scale
+            if dpi < 1 or dpi != int(dpi):
+                raise ValueError(f"dpi {val['dpi']} / scale {scale} is no integer >= 1")
+            scr["dpi"] = int(dpi)
+            scr["position"], scr["observer"] = point(val["position"]), point(val["observer"])
+            if "dimensions" in val:
+                scr["dimensions"] = [scale * float(v) for v in val["dimensions"]]
+            s[key] = scr
+        elif key == "sources":
+            s[key] = []
+            for L in val:
+                _known(L, ("position", "intensity"), key)
+                s[key].append({"position": point(L["position"]),
+                               "intensity": [scale * scale * float(v) for v in L["intensity"]]})
+        elif key == "objects":
+            s[key] = [node(o) for o in val]
+        elif key in ("medium", "background"):
+            s[key] = copy.deepcopy(val)
+        else:
+            raise KeyError(key)
+    return s
+
+
+def _known(body: dict, keys, where: str) -> None:
+    for k in body:
+        if k not in keys:
+            raise KeyError(f"{where}.{k}")
+
+
 # ------------------------------------------------------------ kernel recipes
 # rt_flags (include/rt.h)
 _COUNT, _NO_CULL, _FP32, _NO_BVH, _FORCE_BVH = 1, 2, 4, 8, 16

@@ -97,27 +97,28 @@ def recipe_ref(rt, key, sc, n_cam, n_surf, seed):
     return _refs[key]
 
 
-def oracle_unstable(rt, r, k):
-    """The oracle's own trace of ray k moves under a +-1e-7 shift of the origin."""
+def oracle_unstable(rt, r, k, step=1e-7):
+    """The oracle's own trace of ray k moves under a +-step shift of the origin."""
     for ax in range(3):
         for sgn in (1.0, -1.0):
             o = r.o[k:k + 1].copy()
-            o[0, ax] += sgn * 1e-7
+            o[0, ax] += sgn * step
             rgb, ni, no = rt.oracle_trace(r.sc, o, r.d[k:k + 1])
             if float(np.abs(rgb[0] - r.rgb[k]).max()) > TOL or (ni[0], no[0]) != (r.ni[k], r.no[k]):
                 return True
     return False
 
 
-def check(rt, r, got, what, flags=0):
+def check(rt, r, got, what, flags=0, step=1e-7):
     """got (n, 3) against the oracle at this file's bar, then the rays not left
-    out once more as their own batch: the same colours and the oracle's counts."""
+    out once more as their own batch: the same colours and the oracle's counts.
+    step: the instability probe's shift of the origin."""
     n = len(r)
     assert got.shape == (n, 3) and got.dtype == np.float64
     with np.errstate(invalid="ignore"):
         diff = np.abs(got - r.rgb).max(axis=1)
         bad = np.flatnonzero(~(diff <= TOL))
-    left_out = [int(k) for k in bad if oracle_unstable(rt, r, k)]
+    left_out = [int(k) for k in bad if oracle_unstable(rt, r, k, step)]
     wrong = sorted(set(bad.tolist()) - set(left_out))
     keep = np.ones(n, dtype=bool)
     keep[left_out] = False

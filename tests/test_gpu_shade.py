@@ -47,12 +47,12 @@ def shade(rt, r, sel=slice(None), flags=0, stats=None, wo=None, lights="ref"):
                           r.lights if isinstance(lights, str) else lights, None, flags, stats)
 
 
-def oracle_unstable(rt, r, k, wo, rgb_k, no_k):
-    """oracle_shade of hit k moves under a +-1e-7 shift of p."""
+def oracle_unstable(rt, r, k, wo, rgb_k, no_k, step=1e-7):
+    """oracle_shade of hit k moves under a +-step shift of p."""
     for ax in range(3):
         for sgn in (1.0, -1.0):
             h = r.H[k:k + 1].copy()
-            h["p"][0, ax] += sgn * 1e-7
+            h["p"][0, ax] += sgn * step
             rgb, no = rt.oracle_shade(r.sc, h, wo[k:k + 1], r.lights)
             with np.errstate(invalid="ignore"):
                 moved = not np.all(np.abs(rgb[0] - rgb_k) <= TOL) if np.isfinite(rgb_k).all() else \
@@ -62,10 +62,11 @@ def oracle_unstable(rt, r, k, wo, rgb_k, no_k):
     return False
 
 
-def check(rt, r, got, what, flags=0, wo=None, ref=None):
+def check(rt, r, got, what, flags=0, wo=None, ref=None, step=1e-7):
     """got (n, 3) against the oracle at this file's bar; then the hits not left
     out once more as their own unmasked batch: the same colours, the oracle's
-    count.  ref: (rgb, no) over all entries when not r's own (another wo)."""
+    count.  ref: (rgb, no) over all entries when not r's own (another wo);
+    step: the instability probe's shift of p."""
     n = len(r)
     wo = r.wo if wo is None else wo
     ref_rgb, ref_no = (r.rgb, r.no) if ref is None else ref
@@ -77,7 +78,7 @@ def check(rt, r, got, what, flags=0, wo=None, ref=None):
         diff = np.where(fin, np.abs(got - ref_rgb), 0.0).max(axis=1)
         same_kind = (fin | ((got == ref_rgb) | (np.isnan(got) & np.isnan(ref_rgb)))).all(axis=1)
         bad = np.flatnonzero(r.hit & ~((diff <= TOL) & same_kind))
-    left_out = [int(k) for k in bad if oracle_unstable(rt, r, k, wo, ref_rgb[k], ref_no[k])]
+    left_out = [int(k) for k in bad if oracle_unstable(rt, r, k, wo, ref_rgb[k], ref_no[k], step)]
     wrong = sorted(set(bad.tolist()) - set(left_out))
     keep = r.hit.copy()
     keep[left_out] = False
