@@ -31,6 +31,10 @@
  *                               raytracer/src/tracer.cpp:12-73
  *   rt_query_shade           <- shade_lambert_phong, a batch of hits
  *                               raytracer/src/shading.cpp:31-138
+ *   rt_camera_rays           <- Camera::generate_ray / generate_ray_subpixel for
+ *                               the pixels of a set of rows, raytracer/src/camera.h:44-78
+ *   rt_resolve_samples       <- the frame's sample sum and scale
+ *                               raytracer/src/tracer.cpp:291-296
  *   rt_framebuffer_to_rgb8   <- framebuffer_to_mat_bgr8 / toByte
  *                               raytracer/src/main.cpp:19-34, core.h:313-316
  *   rt_write_png             <- cv::imwrite (main.cpp:86-89)
@@ -66,8 +70,11 @@ extern "C" {
                               (still 6: the batched ray queries rt_query_intersect /
                                rt_query_occluded and their *_device forms, rt_ray and
                                rt_hit, are pure additions, as are the radiance queries
-                               rt_query_radiance / rt_query_radiance_device and the
-                               shading queries rt_query_shade / rt_query_shade_device) */
+                               rt_query_radiance / rt_query_radiance_device, the
+                               shading queries rt_query_shade / rt_query_shade_device,
+                               and the camera rays and sample resolve rt_camera_rays /
+                               rt_camera_rays_device / rt_resolve_samples /
+                               rt_resolve_samples_device) */
 
 /* ---------------------------------------------------------------- errors */
 enum rt_status {
@@ -513,6 +520,65 @@ int rt_query_shade(const rt_scene* s, const rt_hit* hits_host, const double* wo_
 int rt_query_shade_device(const rt_scene* s, const rt_hit* hits_dev, const double* wo_dev, const uint8_t* hit_mask_dev,
                           size_t n, const rt_light* lights, int n_lights, const double* miss_rgb, int flags,
                           double* rgb_dev, void* hip_stream, rt_stats* stats);
+
+/* ------------------------------------- camera rays and sample resolve
+ * The first and the last link of a frame composed from the queries, on the
+ * device: Camera::generate_ray / Camera::generate_ray_subpixel
+ * (camera.h:44-78) for every pixel of a set of output rows, and the frame's
+ * `acc += trace(...)` over its samples followed by `acc * (1.0 / spp)`
+ * (tracer.cpp:291-296).  So
+ *   frame = rt_resolve_samples(rt_query_radiance(rt_camera_rays(camera)))
+ * with every buffer on the device, and because the camera is an argument the
+ * same resident scene can be rendered from another camera (a moved eye, a
+ * stereo pair, a crop at another dpi) without a new scene handle.
+ *
+ * cam: any camera; &rt_scene_get_desc(s)->camera is the scene's.  W, H mean
+ * what they mean for rt_render; the camera's own nx x ny (rt_camera_width /
+ * rt_camera_height) enter the formulas exactly as in the frames.  rows_host
+ * lists OUTPUT rows, top row first, distinct, in any order, as for
+ * rt_render_rows_device; NULL with n_rows == H: all rows in order.  A
+ * duplicate or out-of-range row is RT_ERR_INVALID_ARG.  List entry ri, column
+ * x (and sample s) go to
+ *   rays[ri*W + x]                  RT_RAYS_CENTRE
+ *   rays[(ri*W + x)*RT_SPP + s]     RT_RAYS_JITTERED, samples in the order the
+ *                                   frame sums them.
+ * RT_RAYS_CENTRE: Camera::generate_ray(x, row), including camera.h:47-49 (a
+ * pixel outside the camera's nx x ny gives Ray{eye, (0, 0, -1)}).
+ * RT_RAYS_JITTERED: output row r is loop row y = H-1-r (tracer.cpp:297);
+ * sample s of pixel (x, y) takes draws 2*((y*W + x)*8 + s) and + 1 of the
+ * reference's std::mt19937(12345) stream as (dx, dy), and the ray is
+ * generate_ray_subpixel(x, y, dx, dy).  The draws are the frames' own: they
+ * live in the frames' jitter cache under the frames' key (W, H, rows), so a
+ * standard frame of the same size and rows after this call generates nothing,
+ * nor this call after such a frame (RT_JITTER_CACHE_MB = 0 or a request beyond
+ * the budget: generated into a transient buffer, as for such a frame).
+ * o and d are what the reference's Ray holds; tmin = 1e-4 and tmax = +inf, the
+ * interval Tracer::trace, trace_paper and get_edge_strength query: the output
+ * is valid input for rt_query_intersect[_device] and
+ * rt_query_radiance[_device] as it is.
+ * n_rows == 0 is RT_OK without a launch.  NULL cam, W <= 0, H <= 0, an unknown
+ * kind, or a NULL output with n_rows > 0 is RT_ERR_INVALID_ARG; every argument
+ * check comes before any device work.  stats (may be NULL): pixels = n_rows*W,
+ * ms_rng (the jitter generation; ~0 when the draws were resident), ms_kernel,
+ * ms_total, n_gpus = 1; the ray counts are 0.  Both forms use the current HIP
+ * device, wait for an open frame of the device and block until done; the host
+ * form runs the device form's kernel over row chunks of bounded size through
+ * the queries' staging buffer. */
+enum rt_camera_rays_kind { RT_RAYS_CENTRE = 0, RT_RAYS_JITTERED = 1 };
+#define RT_SPP 8   /* samples per pixel of a standard frame (tracer.cpp:283) */
+int rt_camera_rays_device(const rt_camera* cam, int W, int H, int kind, const int32_t* rows_host, int n_rows,
+                          rt_ray* rays_dev, void* hip_stream, rt_stats* stats);
+int rt_camera_rays(const rt_camera* cam, int W, int H, int kind, const int32_t* rows_host, int n_rows,
+                   rt_ray* rays_host, rt_stats* stats);
+/* fb[3p + c] = (((0 + rgb[(p*spp + 0)*3 + c]) + rgb[(p*spp + 1)*3 + c]) + ...)
+ * * (1.0 / spp) for p < n_pixels, c < 3, in that order: the frame's own sum and
+ * scale for spp = RT_SPP.  1 <= spp <= 64, anything else is
+ * RT_ERR_INVALID_ARG, as is a NULL buffer with n_pixels > 0 or an fb that
+ * overlaps rgb.  n_pixels == 0 is RT_OK.  The device form runs on hip_stream
+ * (NULL = the default stream) of the current device and blocks until done; the
+ * host form is a plain loop in librt_host.so and needs no device. */
+int rt_resolve_samples_device(const double* rgb_dev, size_t n_pixels, int spp, double* fb_dev, void* hip_stream);
+int rt_resolve_samples(const double* rgb_host, size_t n_pixels, int spp, double* fb_host);
 
 /* ------------------------------------------------------------ host I/O */
 /* toByte(v) = round(clamp01(v)*255) (core.h:316), RGB order. */

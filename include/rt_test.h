@@ -5,6 +5,7 @@
 #ifndef RT_TEST_H
 #define RT_TEST_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -262,7 +263,8 @@ int rt_test_paper_order(int32_t* list, int n, const uint32_t* cost, int n_cost);
  * the calling thread's workspace on the current device; _slot: of workspace
  * slot `slot` there (0 the process's own, r + 1 simulated rank r's, which
  * rt_test_dist_threads empties when it returns: entries and bytes are then
- * 0, the counts stay).  hits = standard frames that ran no jitter fill,
+ * 0, the counts stay).  hits = standard frames (and jittered rt_camera_rays
+ * calls, which take their draws as a frame does) that ran no jitter fill,
  * misses = those that ran it (cached or not), entries / bytes = the cached
  * buffers now (the uncached buffer is not counted).  The counts run from
  * process start or the last rt_test_jitter_cache_budget; rt_shutdown frees
@@ -278,6 +280,11 @@ int rt_test_jitter_cache_budget(int64_t bytes);
  * script (jitter_cache.hpp jitter_cache_sim: ops[5 * n_ops] in, out[8 * n_ops]).
  * Returns what it returns, or RT_ERR_INVALID_ARG. */
 int rt_test_jitter_cache_sim(const int64_t* ops, int n_ops, int64_t budget, int64_t* out);
+/* Rays of one staging chunk of rt_camera_rays' host form (default 2^20, the
+ * queries' chunk; a chunk is whole rows, at least one): n rays from here on,
+ * 0: back to the default.  So that a small frame crosses several chunks.
+ * Process-wide; host only. */
+int rt_test_camera_chunk_rays(size_t n);
 /* GPU: one simulated rank (rank of world) of a distributed frame on the
  * current device through the product's rank path, the RCCL gather replaced by
  * a device copy (rank 0 also places every slot).  Ranks are cached, so a

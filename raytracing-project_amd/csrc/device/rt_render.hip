@@ -21,11 +21,16 @@
 // kernels in rt_radiance_kernels.hpp.
 // Shading queries (rt_query_shade, shade_lambert_phong for caller-given hits,
 // shading.cpp:31-138): shade_impl next to it; kernels in rt_shade_kernels.hpp.
+// Camera rays and sample resolve (rt_camera_rays / rt_resolve_samples_device,
+// camera.h:44-78 and tracer.cpp:291-296): camera_rays_impl, on the frames'
+// jitter draws (jitter_plan_ready / jitter_draws, shared with frame_begin);
+// kernels in rt_camera_f64.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -41,6 +46,7 @@
 #include "pinned.hpp"
 #include "mt_poly.hpp"
 #include "rt.h"
+#include "rt_camera.hpp"
 #include "rt_devbuf.hpp"
 #include "rt_launch.hpp"
 #include "rt_internal.hpp"
@@ -183,6 +189,7 @@ struct Workspace {
     DBuf q_rays, q_hits, q_mask, q_rgb;       // ray queries from host memory: one chunk's rays / hits / flags / colours
     DBuf q_wo;                                // shading queries from host memory: one chunk's view directions
     DBuf q_lights;                            // a shading query's own point lights (never the resident scene's `lights`)
+    DBuf cam_rows;                            // rt_camera_rays, centre rays: a rows list that is not 0, 1, 2, ...
     rtamd::JitterTable jtab;                  // mt19937(12345) checkpoint table (resident)
     rtamd::JitterJob jjob;
     rtamd::PinnedArena up;                    // page-locked staging of a frame's uploads (pinned.hpp)
@@ -471,6 +478,63 @@ int counters_ready(Workspace& ws, hipStream_t st) {
     return RT_OK;
 }
 
+// The jitter draws of a standard frame's rows, for the frame (frame_begin) and
+// for the frame's rays (camera_rays_impl, jittered) alike, in two steps around
+// the caller's ms_rng event.  The caller holds the workspace lock, has reset
+// the staging arena, and reports its successful end with ws.jcache.complete.
+//
+// 1. the plan of (W, H, rows), and the checkpoint table reaching the last loop
+//    row's stream words (built on the first use, extended only for a larger frame)
+int jitter_plan_ready(Workspace& ws, int W, int H, const int32_t* rows_host, int n_rows, hipStream_t st,
+                      rtamd::StdPlan& plan) {
+    plan = rtamd::plan_std_frame(W, H, rows_host, n_rows, (int64_t)rtamd::kTableK * 624);
+    try {   // (the jump polynomials: file read or GF(2) arithmetic, may throw)
+        if (plan.n_ckpt > ws.jtab.n_ck) {   // a build or an extension: synchronous
+            const auto t_j = SClock::now();
+            HIP_TRY(ws.jtab.ensure(plan.n_ckpt, st));
+            std::lock_guard<std::mutex> lk(g_setup.mu);
+            g_setup.jtable_ms += ms_since(t_j);
+        }
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("jitter checkpoint table: ") + e.what());
+        return RT_ERR_PROCESSING;
+    }
+    return RT_OK;
+}
+
+// 2. the buffer holding the draws and the rows / jitter-row lists, which are a
+//    function of (W, H, rows) alone: a key resident in the workspace (its
+//    filling call ended successfully, so the draws are complete whatever
+//    stream this call runs on) uploads and generates nothing; otherwise the
+//    rows upload and the fill are enqueued on st.  *filled (may be null):
+//    whether the fill was launched.
+int jitter_draws(Workspace& ws, const char* what, int W, int H, int n_rows, const rtamd::StdPlan& sp, hipStream_t st,
+                 rtamd::JitterCache::Entry** ent, bool* filled = nullptr) {
+    if (filled) *filled = false;
+    const rtamd::JitterCache::Got got = ws.jcache.acquire(W, H, sp.rows_jrow, (size_t)n_rows * 16 * W * sizeof(double),
+                                                          rtamd::jitter_cache_budget());
+    if (!got.e) {
+        rtamd::set_last_error(std::string(what) + ": out of device memory for the frame's jitter draws");
+        return RT_ERR_HIP;
+    }
+    *ent = got.e;
+    if (got.upload_rows)
+        HIP_TRY(rtamd::upload_async(&ws.up, got.e->rows(), sp.rows_jrow.data(), sp.rows_jrow.size() * sizeof(int32_t), st));
+    if (got.fill) {
+        HIP_TRY(ws.jscratch.ensure(rtamd::mt_fill_scratch_bytes(sp.jranges)));
+        ws.jjob.up = &ws.up;
+        const auto t_l = SClock::now();
+        HIP_TRY(rtamd::mt_launch_fill(ws.jtab, sp.jranges, ws.jjob, ws.jscratch.p, got.e->jit(), st));
+        if (filled) *filled = true;
+        {
+            std::lock_guard<std::mutex> lk(g_setup.mu);
+            if (!g_setup.jitter_launched) g_setup.jitter_launch_ms = ms_since(t_l);
+            g_setup.jitter_launched = true;
+        }
+    }
+    return RT_OK;
+}
+
 int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int32_t* rows_host, int n_rows,
                 hipStream_t st, rt_frame** out) {
     const auto t_start = std::chrono::steady_clock::now();
@@ -554,50 +618,15 @@ int frame_begin(const rt_scene* s, int W, int H, int mode, int flags, const int3
     }
 
     if (n_rows > 0 && mode == RT_MODE_STANDARD) {
-        f->std_plan = rtamd::plan_std_frame(W, H, rows_host, n_rows, (int64_t)rtamd::kTableK * 624);
-        // the checkpoint table must reach the last loop row's stream words
-        // (built on the first frame, extended only for a larger frame)
-        try {   // (the jump polynomials: file read or GF(2) arithmetic, may throw)
-            if (f->std_plan.n_ckpt > ws.jtab.n_ck) {   // a build or an extension: synchronous
-                const auto t_j = SClock::now();
-                HIP_TRY(ws.jtab.ensure(f->std_plan.n_ckpt, st));
-                std::lock_guard<std::mutex> lk(g_setup.mu);
-                g_setup.jtable_ms += ms_since(t_j);
-            }
-        } catch (const std::exception& e) {
-            rtamd::set_last_error(std::string("jitter checkpoint table: ") + e.what());
-            return RT_ERR_PROCESSING;
-        }
+        const int rv = jitter_plan_ready(ws, W, H, rows_host, n_rows, st, f->std_plan);
+        if (rv != RT_OK) return rv;
     }
     HIP_TRY(hipEventRecord(ws.ev[0], st));
     if (n_rows > 0 && mode == RT_MODE_STANDARD) {
-        const rtamd::StdPlan& sp = f->std_plan;
-        // the draws and the rows / jitter-row lists are a function of (W, H,
-        // rows) alone: a frame whose key is resident in the workspace (its
-        // filling frame ended successfully, so the draws are complete
-        // whatever stream this frame runs on) uploads and generates nothing
-        const rtamd::JitterCache::Got got = ws.jcache.acquire(W, H, sp.rows_jrow, (size_t)n_rows * 16 * W * sizeof(double),
-                                                              rtamd::jitter_cache_budget());
-        if (!got.e) {
-            rtamd::set_last_error("rt_render: out of device memory for the frame's jitter draws");
-            return RT_ERR_HIP;
-        }
-        f->jent = got.e;
-        f->jit = got.e->jit();
-        f->rows = got.e->rows();
-        if (got.upload_rows)
-            HIP_TRY(rtamd::upload_async(&ws.up, got.e->rows(), sp.rows_jrow.data(), sp.rows_jrow.size() * sizeof(int32_t), st));
-        if (got.fill) {
-            HIP_TRY(ws.jscratch.ensure(rtamd::mt_fill_scratch_bytes(sp.jranges)));
-            ws.jjob.up = &ws.up;
-            const auto t_l = SClock::now();
-            HIP_TRY(rtamd::mt_launch_fill(ws.jtab, sp.jranges, ws.jjob, ws.jscratch.p, got.e->jit(), st));
-            {
-                std::lock_guard<std::mutex> lk(g_setup.mu);
-                if (!g_setup.jitter_launched) g_setup.jitter_launch_ms = ms_since(t_l);
-                g_setup.jitter_launched = true;
-            }
-        }
+        const int rv = jitter_draws(ws, "rt_render", W, H, n_rows, f->std_plan, st, &f->jent);
+        if (rv != RT_OK) return rv;
+        f->jit = f->jent->jit();
+        f->rows = f->jent->rows();
     } else if (n_rows > 0) {
         f->paper = rtamd::plan_paper_frame(rtamd::scene_uid(s), W, H, mode, flags, rows_host, n_rows);
         f->paper_calls.reset(&f->paper);
@@ -1118,7 +1147,152 @@ int shade_impl(const char* what, const rt_scene* s, const rt_hit* hits, const do
     return RT_OK;
 }
 
+// ------------------------------------------------------------- camera rays
+// Rays of one chunk of rt_camera_rays (the host form): the queries' chunk, so
+// the same staging buffer (q_rays) serves; rt_test_camera_chunk_rays sets
+// another size (0: back to this one).
+std::atomic<size_t> g_camera_chunk_rays{kQueryChunkRays};
+
+// rt_camera_rays[_device]: the rays of list entries [0, n_rows) of a W x H
+// frame seen through cam (k_camera_rays, rt_camera_f64.hip).  host: rays is
+// host memory, filled through the workspace's ray staging buffer in row chunks
+// of at most g_camera_chunk_rays rays (at least one row); else device memory,
+// written in place on st.  Jittered rays read the frames' draws (jitter_plan_ready
+// / jitter_draws: the frames' plan, checkpoint table, cache key and fill), one
+// acquisition for the whole list whatever the chunks.  Holds the workspace
+// lock like a frame, and returns with st drained.
+int camera_rays_impl(const char* what, const rt_camera* cam, int W, int H, int kind, const int32_t* rows_host, int n_rows,
+                     rt_ray* rays, bool host, hipStream_t st, rt_stats* stats) {
+    const auto t_start = SClock::now();
+    const auto fail = [what](const char* msg, int rc) {
+        rtamd::set_last_error(std::string(what) + ": " + msg);
+        return rc;
+    };
+    if (!cam) return fail("cam is NULL", RT_ERR_INVALID_ARG);
+    if (W <= 0 || H <= 0) return fail("W and H must be > 0", RT_ERR_INVALID_ARG);
+    if (kind != RT_RAYS_CENTRE && kind != RT_RAYS_JITTERED) return fail("unknown kind", RT_ERR_INVALID_ARG);
+    if ((size_t)W * RT_SPP >= ((size_t)1 << 31)) return fail("W is beyond one launch's row", RT_ERR_INVALID_ARG);
+    if (n_rows < 0 || n_rows > H) return fail("bad rows", RT_ERR_INVALID_ARG);
+    if (!rows_host && n_rows != 0 && n_rows != H) return fail("rows is NULL with n_rows != H", RT_ERR_INVALID_ARG);
+    const bool jittered = kind == RT_RAYS_JITTERED;
+    std::vector<int32_t> all_rows;
+    bool in_order = true;   // entry ri is row ri
+    if (!rows_host) {
+        all_rows.resize(n_rows);
+        for (int r = 0; r < n_rows; ++r) all_rows[r] = r;
+        rows_host = all_rows.data();
+    } else {
+        std::vector<char> seen(H, 0);
+        for (int i = 0; i < n_rows; ++i) {
+            if (rows_host[i] < 0 || rows_host[i] >= H) return fail("row out of range", RT_ERR_INVALID_ARG);
+            if (seen[rows_host[i]]++) return fail("duplicate row", RT_ERR_INVALID_ARG);
+            in_order = in_order && rows_host[i] == i;
+        }
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->n_gpus = 1;
+    }
+    if (n_rows == 0) return RT_OK;
+    if (!rays) return fail("the ray buffer is NULL", RT_ERR_INVALID_ARG);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    Workspace& ws = workspace(dev);
+    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
+    // (as query_impl: nothing of this call stays queued on st when the lock goes)
+    struct Drain {
+        hipStream_t st;
+        ~Drain() { (void)hipStreamSynchronize(st); }
+    } drain{st};
+    ws.up.reset();   // (the previous frame's or query's uploads completed)
+    if (!ws.ev[0]) {
+        rtamd::SetupTimer tm(rtamd::kSetupStreams);
+        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
+    }
+    rtamd::CameraParams P{};
+    for (int i = 0; i < 3; ++i) {
+        P.eye[i] = cam->eye[i];
+        P.P[i] = cam->P[i];
+    }
+    P.Lx = cam->Lx;
+    P.Ly = cam->Ly;
+    P.cam_nx = rt_camera_width(cam);
+    P.cam_ny = rt_camera_height(cam);
+    P.W = W;
+    P.H = H;
+    rtamd::JitterCache::Entry* jent = nullptr;
+    float ms_rng = 0.f;
+    if (jittered) {
+        rtamd::StdPlan plan;   // (host source of the rows upload: alive until st is drained)
+        {
+            const int rv = jitter_plan_ready(ws, W, H, rows_host, n_rows, st, plan);
+            if (rv != RT_OK) return rv;
+        }
+        HIP_TRY(hipEventRecord(ws.ev[0], st));
+        bool filled = false;
+        {
+            const int rv = jitter_draws(ws, what, W, H, n_rows, plan, st, &jent, &filled);
+            if (rv != RT_OK) return rv;
+        }
+        HIP_TRY(hipEventRecord(ws.ev[1], st));
+        // (the plan's vectors must outlive the upload: wait here, once per call)
+        HIP_TRY(hipStreamSynchronize(st));
+        if (filled) rtamd::note_launch("rtamd", "k_mt_fill_w");
+        (void)hipEventElapsedTime(&ms_rng, ws.ev[0], ws.ev[1]);
+        P.rows = jent->rows();
+        P.jrow = jent->rows() + n_rows;
+        P.jit = jent->jit();
+    } else if (!in_order) {
+        HIP_TRY(ws.cam_rows.ensure((size_t)n_rows * sizeof(int32_t)));
+        HIP_TRY(rtamd::upload_async(&ws.up, ws.cam_rows.p, rows_host, (size_t)n_rows * sizeof(int32_t), st));
+        P.rows = ws.cam_rows.as<int32_t>();
+    }
+    const size_t per_row = (size_t)W * (jittered ? RT_SPP : 1);
+    // list entries of one launch: the grid's y extent; of one host chunk: its rays
+    const int launch_rows = 65535;
+    const int chunk_rows =
+        host ? (int)std::min<size_t>((size_t)n_rows, std::max<size_t>(1, g_camera_chunk_rays.load() / per_row)) : n_rows;
+    if (host) HIP_TRY(ws.q_rays.ensure((size_t)chunk_rows * per_row * sizeof(rt_ray)));
+    double ms_kernel = 0.0;
+    for (int c0 = 0; c0 < n_rows; c0 += chunk_rows) {
+        const int cn = std::min(chunk_rows, n_rows - c0);
+        rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays + (size_t)c0 * per_row;
+        HIP_TRY(hipEventRecord(ws.ev[1], st));
+        for (int l0 = 0; l0 < cn; l0 += launch_rows) {
+            P.ri0 = c0 + l0;
+            P.n_rows = std::min(launch_rows, cn - l0);
+            P.rays = d_rays + (size_t)l0 * per_row;
+            HIP_TRY(rtd::launch_camera_rays(jittered, st, P));
+        }
+        HIP_TRY(hipEventRecord(ws.ev[2], st));
+        if (host)
+            HIP_TRY(hipMemcpyAsync(rays + (size_t)c0 * per_row, d_rays, (size_t)cn * per_row * sizeof(rt_ray),
+                                   hipMemcpyDeviceToHost, st));
+        // (the chunk buffer and the events are reused by the next chunk)
+        HIP_TRY(hipStreamSynchronize(st));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) ms_kernel += ms;
+    }
+    // st has run to its end: the draws and the rows list this call wrote are
+    // complete, and later frames or calls of its key may read them
+    ws.jcache.complete(jent);
+    if (stats) {
+        stats->pixels = (uint64_t)n_rows * W;
+        stats->ms_rng = ms_rng;
+        stats->ms_kernel = ms_kernel;
+        stats->ms_total = ms_since(t_start);
+    }
+    return RT_OK;
+}
+
 }  // namespace
+
+extern "C" int rt_test_camera_chunk_rays(size_t n) {
+    g_camera_chunk_rays.store(n ? n : kQueryChunkRays);
+    return RT_OK;
+}
 
 void rtamd::set_workspace_slot(int slot) { t_ws_slot = slot; }
 
@@ -1222,7 +1396,7 @@ int rtamd::release_device_workspaces(int min_slot) {
                         &w->wobjs, &w->wctab, &w->worig, &w->wchunk,
                         &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->ckpt,
                         &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime,
-                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb, &w->q_wo, &w->q_lights})
+                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb, &w->q_wo, &w->q_lights, &w->cam_rows})
             b->release();
         w->jtab.release();
         w->jcache.release();   // every cached entry and the uncached buffer (the hit / miss counts stay)
@@ -1479,6 +1653,38 @@ extern "C" int rt_query_shade_device(const rt_scene* s, const rt_hit* hits_dev, 
                                      rt_stats* stats) {
     return shade_impl("rt_query_shade_device", s, hits_dev, wo_dev, hit_mask_dev, n, lights, n_lights, miss_rgb, flags,
                       rgb_dev, false, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_camera_rays_device(const rt_camera* cam, int W, int H, int kind, const int32_t* rows_host, int n_rows,
+                                     rt_ray* rays_dev, void* hip_stream, rt_stats* stats) {
+    return camera_rays_impl("rt_camera_rays_device", cam, W, H, kind, rows_host, n_rows, rays_dev, false,
+                            (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_camera_rays(const rt_camera* cam, int W, int H, int kind, const int32_t* rows_host, int n_rows,
+                              rt_ray* rays_host, rt_stats* stats) {
+    return camera_rays_impl("rt_camera_rays", cam, W, H, kind, rows_host, n_rows, rays_host, true, nullptr, stats);
+}
+
+extern "C" int rt_resolve_samples_device(const double* rgb_dev, size_t n_pixels, int spp, double* fb_dev,
+                                         void* hip_stream) {
+    const auto fail = [](const char* msg) {
+        rtamd::set_last_error(std::string("rt_resolve_samples_device: ") + msg);
+        return (int)RT_ERR_INVALID_ARG;
+    };
+    if (spp < 1 || spp > 64) return fail("spp must be in [1, 64]");
+    if (!n_pixels) return RT_OK;
+    if (!rgb_dev || !fb_dev) return fail("NULL buffer");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(rgb_dev), b = reinterpret_cast<uintptr_t>(fb_dev);
+    if (b < a + n_pixels * spp * 3 * sizeof(double) && a < b + n_pixels * 3 * sizeof(double)) return fail("fb overlaps rgb");
+    rtamd::ResolveParams P;
+    P.rgb = rgb_dev;
+    P.n_pixels = n_pixels;
+    P.spp = spp;
+    P.fb = fb_dev;
+    HIP_TRY(rtd::launch_resolve_samples((hipStream_t)hip_stream, P));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+    return RT_OK;
 }
 
 extern "C" int rt_scatter_rows_device(const double* src_dev, const int32_t* rows_dev, int n_rows, int W,

@@ -33,6 +33,30 @@ extern "C" int rt_camera_height(const rt_camera* c) {  // camera.h:21
     return n > 1 ? n : 1;
 }
 
+// The frame's `acc += trace(...)` over the samples in order, then
+// `acc * (1.0 / spp)` (tracer.cpp:291-296).  Compiled, like the reference,
+// without FMA contraction (no -march): every add and the multiply round once.
+extern "C" int rt_resolve_samples(const double* rgb, size_t n_pixels, int spp, double* fb) {
+    if (spp < 1 || spp > 64) { set_last_error("rt_resolve_samples: spp must be in [1, 64]"); return RT_ERR_INVALID_ARG; }
+    if (!n_pixels) return RT_OK;
+    if (!rgb || !fb) { set_last_error("rt_resolve_samples: NULL buffer"); return RT_ERR_INVALID_ARG; }
+    const uintptr_t a = reinterpret_cast<uintptr_t>(rgb), b = reinterpret_cast<uintptr_t>(fb);
+    if (b < a + n_pixels * spp * 3 * sizeof(double) && a < b + n_pixels * 3 * sizeof(double)) {
+        set_last_error("rt_resolve_samples: fb overlaps rgb");
+        return RT_ERR_INVALID_ARG;
+    }
+    const double inv = 1.0 / (double)spp;
+    for (size_t p = 0; p < n_pixels; ++p) {
+        const double* src = rgb + p * (size_t)spp * 3;
+        for (int c = 0; c < 3; ++c) {
+            double acc = 0.0;
+            for (int s = 0; s < spp; ++s) acc += src[3 * s + c];
+            fb[3 * p + c] = acc * inv;
+        }
+    }
+    return RT_OK;
+}
+
 static std::atomic<uint64_t> g_next_uid{1};
 
 static rt_scene* wrap(rtamd::SceneIR&& ir) {

@@ -46,6 +46,9 @@ RT_FLAG_NO_CULL = 2
 RT_FLAG_FP32 = 4   # non-parity FP32 fast path
 RT_FLAG_NO_BVH = 8   # wave culls without the wave BVH (A/B; identical results)
 RT_FLAG_FORCE_BVH = 16   # the wave BVH on every frame (no on/off trial frames)
+RT_RAYS_CENTRE = 0     # rt_camera_rays: Camera::generate_ray at the pixel centres
+RT_RAYS_JITTERED = 1   # ... generate_ray_subpixel at the frame's own RT_SPP jitter draws per pixel
+RT_SPP = 8             # samples per pixel of a standard frame (tracer.cpp:283)
 
 NODE_SPHERE, NODE_HALFSPACE, NODE_POKEBALL, NODE_TRANSLATION, NODE_SCALING, NODE_ROTATION, NODE_CSG = range(7)
 CSG_UNION, CSG_INTERSECTION, CSG_DIFFERENCE = range(3)
@@ -161,6 +164,8 @@ def host_lib():
         lib.rt_camera_height.argtypes = [C.POINTER(Camera)]
         lib.rt_framebuffer_to_rgb8.argtypes = [_dp, C.c_size_t, C.POINTER(C.c_uint8)]
         lib.rt_write_png.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]
+        if hasattr(lib, "rt_resolve_samples"):   # (absent only in builds of older sources)
+            lib.rt_resolve_samples.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         _host = lib
     return _host
 
@@ -208,6 +213,13 @@ def amd_lib():
                                                   C.POINTER(Stats)]
             lib.rt_test_shade_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
             lib.rt_test_shade_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
+        if hasattr(lib, "rt_camera_rays"):   # (likewise)
+            lib.rt_camera_rays.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                           C.c_void_p, C.POINTER(Stats)]
+            lib.rt_camera_rays_device.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.rt_resolve_samples_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+            lib.rt_test_camera_chunk_rays.argtypes = [C.c_size_t]
         lib.rt_device_count.restype = C.c_int
         lib.rt_render_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                         C.POINTER(Stats)]
@@ -887,6 +899,91 @@ def shade_rows(table: int) -> list[str]:
     while lib.rt_test_shade_kernel_row(table, len(out), buf, 160) == RT_OK:
         out.append(buf.value.decode())
     return out
+
+
+def _camera_of(cam_or_scene) -> Camera:
+    """An rt_camera: a Camera as it is, or a copy of a Scene's."""
+    if isinstance(cam_or_scene, Camera):
+        return cam_or_scene
+    if isinstance(cam_or_scene, Scene):
+        return Camera.from_buffer_copy(cam_or_scene.desc.camera)
+    raise TypeError(f"expected a Camera or a Scene, got {type(cam_or_scene).__name__}")
+
+
+def _rows_arg(rows, H: int):
+    """(int32 array or None, n_rows) of a rows list; None: all H rows in order."""
+    if rows is None:
+        return None, H
+    arr = np.ascontiguousarray(rows, dtype=np.int32)
+    if arr.ndim != 1:
+        raise ValueError("rows must be a flat list of output rows")
+    return arr, len(arr)
+
+
+def camera_rays(cam_or_scene, W: int, H: int, kind: int, rows=None, stats: Stats | None = None) -> np.ndarray:
+    """rt_camera_rays: the rays of output rows `rows` (None: all, in order) of
+    a W x H frame seen through the camera, as a RAY_DTYPE array of shape
+    (n_rows, W) for RT_RAYS_CENTRE (Camera::generate_ray) or (n_rows, W,
+    RT_SPP) for RT_RAYS_JITTERED (generate_ray_subpixel at the frame's own
+    draws, samples in the order the frame sums them)."""
+    cam = _camera_of(cam_or_scene)
+    arr, n_rows = _rows_arg(rows, H)
+    shape = (n_rows, max(W, 0), RT_SPP) if kind == RT_RAYS_JITTERED else (n_rows, max(W, 0))
+    rays = np.zeros(shape, dtype=RAY_DTYPE)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_camera_rays(C.byref(cam), W, H, kind,
+                                  arr.ctypes.data_as(C.POINTER(C.c_int32)) if arr is not None else None, n_rows,
+                                  rays.ctypes.data_as(C.c_void_p), C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return rays
+
+
+def camera_rays_device(cam_or_scene, W: int, H: int, kind: int, rows, rays_dev: DeviceBuffer,
+                       stream: Stream | None = None, stats: Stats | None = None) -> int:
+    """rt_camera_rays_device: the same rays into rays_dev, on `stream` (None:
+    the default stream).  Returns the number of rays written."""
+    cam = _camera_of(cam_or_scene)
+    arr, n_rows = _rows_arg(rows, H)
+    n = n_rows * max(W, 0) * (RT_SPP if kind == RT_RAYS_JITTERED else 1)
+    if rays_dev.nbytes < n * RAY_DTYPE.itemsize:
+        raise ValueError("camera_rays_device: the ray buffer is too small")
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_camera_rays_device(C.byref(cam), W, H, kind,
+                                         arr.ctypes.data_as(C.POINTER(C.c_int32)) if arr is not None else None, n_rows,
+                                         rays_dev.ptr, stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return n
+
+
+def resolve_samples(rgb, spp: int) -> np.ndarray:
+    """rt_resolve_samples (host): rgb (..., spp, 3) summed over the samples in
+    order and scaled by 1.0 / spp, as the frame does (tracer.cpp:291-296)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    if rgb.ndim < 2 or rgb.shape[-1] != 3 or rgb.shape[-2] != spp:
+        raise ValueError(f"rgb must have shape (..., {spp}, 3), got {rgb.shape}")
+    fb = np.zeros(rgb.shape[:-2] + (3,), dtype=np.float64)
+    rc = host_lib().rt_resolve_samples(rgb.ctypes.data_as(C.c_void_p), fb.size // 3, spp, fb.ctypes.data_as(C.c_void_p))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return fb
+
+
+def resolve_samples_device(rgb_dev: DeviceBuffer, n_pixels: int, spp: int, fb_dev: DeviceBuffer,
+                           stream: Stream | None = None) -> None:
+    """rt_resolve_samples_device: the first n_pixels * spp colours of rgb_dev
+    into the first n_pixels colours of fb_dev, on `stream`."""
+    if n_pixels < 0 or rgb_dev.nbytes < n_pixels * max(spp, 0) * 24 or fb_dev.nbytes < n_pixels * 24:
+        raise ValueError("resolve_samples_device: a buffer is too small")
+    rc = amd_lib().rt_resolve_samples_device(rgb_dev.ptr, n_pixels, spp, fb_dev.ptr, stream.handle if stream else None)
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def camera_chunk_rays(n: int) -> None:
+    """rt_test_camera_chunk_rays: rays per staging chunk of camera_rays (0: the default)."""
+    _ok(amd_lib().rt_test_camera_chunk_rays(n), "rt_test_camera_chunk_rays")
 
 
 def render_multi(scene: Scene, width: int, height: int, mode: int, n_gpus: int, flags: int = RT_FLAG_NONE,

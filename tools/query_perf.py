@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Ray-query throughput on config 5 at 7680x4320 (GPU box; DESIGN.md §Ray
 queries): rt_query_intersect_device over the frame's pixel-centre camera rays
+(generated on the device by rt_camera_rays_device)
 
   coherent   in row-major pixel order (a wave = 64 consecutive pixels of a row)
   shuffled   the same rays in a random order (every wave incoherent)
@@ -20,7 +21,6 @@ import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -31,24 +31,15 @@ import rtamd  # noqa: E402
 import scenes  # noqa: E402
 
 
-def camera_rays(sc) -> np.ndarray:
+def camera_rays(sc, d_rays) -> int:
     """Camera::generate_ray (camera.h:44-58) of every pixel, row-major from the
-    top row: the rays k_paper_primary generates on the device."""
-    cam = sc.desc.camera
-    W, H = sc.width, sc.height
-    eye, P = np.array(cam.eye[:]), np.array(cam.P[:])
-    sx = (np.arange(W, dtype=np.float64) + 0.5) / W
-    sy = ((H - 1 - np.arange(H, dtype=np.float64)) + 0.5) / H
-    rays = np.empty(W * H, dtype=rtamd.RAY_DTYPE)
-    d = rays["d"].reshape(H, W, 3)
-    d[:, :, 0] = (P[0] + cam.Lx * sx - eye[0])[None, :]
-    d[:, :, 1] = (P[1] + cam.Ly * sy - eye[1])[:, None]
-    d[:, :, 2] = P[2] - eye[2]
-    d /= np.sqrt((d * d).sum(axis=2, keepdims=True))
-    rays["o"] = eye
-    rays["tmin"] = 1e-4
-    rays["tmax"] = np.inf
-    return rays
+    top row, generated on the device (rt_camera_rays_device; held bit-equal to
+    the oracle by tests/test_gpu_camera_rays.py): the rays k_paper_primary
+    generates itself."""
+    st = rtamd.Stats()
+    n = rtamd.camera_rays_device(sc, sc.width, sc.height, rtamd.RT_RAYS_CENTRE, None, d_rays, stats=st)
+    print(f"{n} camera rays generated on the device: ms_kernel {st.ms_kernel:.3f}", flush=True)
+    return n
 
 
 def frame_times(sc, reps):
@@ -107,23 +98,14 @@ def main():
     print(f"paper frame {W}x{H} (k_paper_primary* + k_paper_finish): ms_kernel min {min(ft):.3f} median "
           f"{np.median(ft):.3f}", flush=True)
     if not a.frames_only:
-        t0 = time.time()
-        rays = camera_rays(sc)
-        # the host formula against the oracle's Camera::generate_ray at a few pixels
-        if os.path.exists(os.path.join(rtamd.ORACLE_DIR, "liboracle.so")):
-            o3, d3 = (C.c_double * 3)(), (C.c_double * 3)()
-            for (i, j) in ((0, 0), (W - 1, H - 1), (W // 3, H // 2), (17, H - 5)):
-                rtamd.oracle_lib().oracle_camera_ray(sc.desc_ptr, i, j, 0.0, 0.0, 0, o3, d3)
-                assert np.allclose(rays["d"][j * W + i], list(d3), rtol=0, atol=1e-14), (i, j)
         d_rays, d_hits, d_mask = rtamd.DeviceBuffer(n * 64), rtamd.DeviceBuffer(n * 64), rtamd.DeviceBuffer(n)
-        print(f"{n} camera rays built in {time.time() - t0:.1f} s", flush=True)
-        cases = [("coherent", rays)]
+        assert camera_rays(sc, d_rays) == n
+        # coherent: the device's rays as they are; shuffled: one round trip to permute them
         perm = np.random.default_rng(12345).permutation(n)
-        cases.append(("shuffled", None))
+        cases = [("coherent", None), ("shuffled", perm)]
         for tag, r in cases:
-            if r is None:
-                r = rays[perm]
-            d_rays.from_host(r)
+            if r is not None:
+                d_rays.from_host(d_rays.to_host(np.uint8).view(rtamd.RAY_DTYPE)[r])
             qt = query_times(sc, d_rays, n, d_hits, d_mask, a.reps, False)
             hit = int(d_mask.to_host(np.uint8).sum())
             res[tag] = {"ms_kernel": {"min": min(qt), "median": float(np.median(qt)), "all": qt},
@@ -134,7 +116,6 @@ def main():
                 ot = query_times(sc, d_rays, n, d_hits, d_mask, a.reps, True)
                 res[tag]["occluded_ms_kernel"] = {"min": min(ot), "median": float(np.median(ot)), "all": ot}
                 print(f"query_occluded  {tag:9s}: ms_kernel min {min(ot):.3f}  {rate(min(ot)):.0f} Mrays/s", flush=True)
-            del r
         assert res["coherent"]["hits"] == res["shuffled"]["hits"]
         res["kernel"] = rtamd.query_kernel_name(sc, 0)[1]
     line = json.dumps(res)

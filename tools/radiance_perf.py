@@ -20,7 +20,6 @@ import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -30,37 +29,15 @@ sys.path.insert(0, os.path.join(REPO, "raytracing-project_amd", "python"))
 import rtamd  # noqa: E402
 import scenes  # noqa: E402
 
-_dp = C.POINTER(C.c_double)
-
-
-def frame_rays(sc) -> np.ndarray:
-    """The frame's jittered rays (tracer.cpp:284-293, camera.h:68-78) as an
-    rt_ray array in frame order (output row, x, sample)."""
-    cam = sc.desc.camera
-    W, H = sc.width, sc.height
-    jit = np.zeros(16 * W * H)
-    rtamd.oracle_lib().oracle_jitter(0, len(jit), jit.ctypes.data_as(_dp))
-    jit = jit.reshape(H, W, 8, 2)   # (loop row, x, sample, dx / dy)
-    eye, P = np.array(cam.eye[:]), np.array(cam.P[:])
-    rays = np.empty(H * W * 8, dtype=rtamd.RAY_DTYPE)
-    d = rays["d"].reshape(H, W, 8, 3)
-    for r in range(H):   # output row r is loop row y = H - 1 - r
-        y = H - 1 - r
-        sx = (np.arange(W, dtype=np.float64)[:, None] + 0.5 + jit[y, :, :, 0]) / W
-        sy = (y + 0.5 + jit[y, :, :, 1]) / H
-        d[r, :, :, 0] = P[0] + cam.Lx * sx - eye[0]
-        d[r, :, :, 1] = P[1] + cam.Ly * sy - eye[1]
-        d[r, :, :, 2] = P[2] - eye[2]
-    d /= np.sqrt((d * d).sum(axis=3, keepdims=True))
-    rays["o"] = eye
-    rays["tmin"] = 1e-4
-    rays["tmax"] = np.inf
-    # the host formula against the oracle's Camera::generate_ray_subpixel at a few samples
-    o3, d3 = (C.c_double * 3)(), (C.c_double * 3)()
-    for (x, y, s) in ((0, 0, 0), (W - 1, H - 1, 7), (W // 3, H // 2, 3), (17, H - 5, 5)):
-        rtamd.oracle_lib().oracle_camera_ray(sc.desc_ptr, x, y, jit[y, x, s, 0], jit[y, x, s, 1], 1, o3, d3)
-        assert np.allclose(d[H - 1 - y, x, s], list(d3), rtol=0, atol=1e-14), (x, y, s)
-    return rays
+def frame_rays(sc, d_rays) -> int:
+    """The frame's jittered rays (tracer.cpp:284-293, camera.h:68-78) in frame
+    order (output row, x, sample), generated on the device from the frame's own
+    resident draws (rt_camera_rays_device; held bit-equal to the oracle by
+    tests/test_gpu_camera_rays.py)."""
+    st = rtamd.Stats()
+    n = rtamd.camera_rays_device(sc, sc.width, sc.height, rtamd.RT_RAYS_JITTERED, None, d_rays, stats=st)
+    print(f"{n} frame rays generated on the device: ms_rng {st.ms_rng:.3f} ms_kernel {st.ms_kernel:.3f}", flush=True)
+    return n
 
 
 def frame_times(sc, reps):
@@ -106,16 +83,13 @@ def main():
     print(f"standard frame {W}x{H} ({res['frame_kernel']}): ms_kernel min {min(ft):.3f} median {np.median(ft):.3f} "
           f"max {max(ft):.3f}", flush=True)
     if not a.frames_only:
-        t0 = time.time()
-        rays = frame_rays(sc)
-        print(f"{n} frame rays built in {time.time() - t0:.1f} s", flush=True)
         d_rays, d_rgb = rtamd.DeviceBuffer(n * 64), rtamd.DeviceBuffer(n * 24)
+        assert frame_rays(sc, d_rays) == n
         res["kernel"] = rtamd.radiance_kernel_name(sc)[1]
         perm = np.random.default_rng(12345).permutation(n)
         for tag in ("frame", "shuffled"):
-            r = rays if tag == "frame" else rays[perm]
-            d_rays.from_host(r)
-            del r
+            if tag == "shuffled":   # (one round trip to permute the device's rays)
+                d_rays.from_host(d_rays.to_host(np.uint8).view(rtamd.RAY_DTYPE)[perm])
             st = rtamd.Stats()
             qt = []
             for k in range(1 + a.reps):
@@ -127,8 +101,8 @@ def main():
                         "vs_frame_median": float(np.median(qt)) / float(np.median(ft))}
             print(f"query_radiance {tag:9s}: ms_kernel min {min(qt):.3f} median {np.median(qt):.3f} max {max(qt):.3f}  "
                   f"{n / min(qt) / 1e3:.0f} Mrays/s  {res[tag]['vs_frame_median']:.2f}x the frame", flush=True)
-            # the same rays as the frame up to the last bit of numpy's normalisation:
-            # its ray counts (reported, not asserted), and (frame order) its pixels
+            # the frame's own rays: its ray counts (reported, not asserted), and
+            # (frame order) its pixels
             res[tag]["rays_equal_frame"] = res[tag]["rays"] == res["frame_rays"]
             if tag == "frame":
                 rgb = d_rgb.to_host(np.float64, (H, W, 8, 3))

@@ -27,31 +27,6 @@ import rtamd  # noqa: E402
 import scenes  # noqa: E402
 
 
-def centre_rays(sc) -> np.ndarray:
-    """The pixel-centre camera rays (Camera::generate_ray, camera.h) as an
-    rt_ray array in frame order (output row, x)."""
-    cam = sc.desc.camera
-    W, H = sc.width, sc.height
-    eye, P = np.array(cam.eye[:]), np.array(cam.P[:])
-    rays = np.empty(H * W, dtype=rtamd.RAY_DTYPE)
-    d = rays["d"].reshape(H, W, 3)
-    sx = (np.arange(W, dtype=np.float64) + 0.5) / W
-    for r in range(H):   # output row r: jf = H - 1 - r (camera.h:51)
-        sy = (H - 1 - r + 0.5) / H
-        d[r, :, 0] = P[0] + cam.Lx * sx - eye[0]
-        d[r, :, 1] = P[1] + cam.Ly * sy - eye[1]
-        d[r, :, 2] = P[2] - eye[2]
-    d /= np.sqrt((d * d).sum(axis=2, keepdims=True))
-    rays["o"] = eye
-    rays["tmin"] = 1e-4
-    rays["tmax"] = np.inf
-    o3, d3 = (C.c_double * 3)(), (C.c_double * 3)()
-    for (x, y) in ((0, 0), (W - 1, H - 1), (W // 3, H // 2)):   # against the oracle's camera
-        rtamd.oracle_lib().oracle_camera_ray(sc.desc_ptr, x, y, 0.0, 0.0, 0, o3, d3)
-        assert np.allclose(d[y, x], list(d3), rtol=0, atol=1e-14), (x, y)   # (generate_ray's j is the output row)
-    return rays
-
-
 def summary(ms):
     return {"min": min(ms), "median": float(np.median(ms)), "max": max(ms), "all": ms}
 
@@ -67,14 +42,15 @@ def main():
     rec1 = rtamd.with_recursion_limit(sc, 1)
     W, H = sc.width, sc.height
     n = W * H
-    rays = centre_rays(sc)
     res = {"scene": "config 4", "W": W, "H": H, "rays": n, "kernels": {
         "intersect": rtamd.query_kernel_name(sc, 0)[1], "shade": rtamd.shade_kernel_name(sc)[1],
         "radiance": rtamd.radiance_kernel_name(rec1)[1]}}
     d_rays, d_hits, d_mask = rtamd.DeviceBuffer(n * 64), rtamd.DeviceBuffer(n * 64), rtamd.DeviceBuffer(n)
     d_wo, d_rgb, d_rad = rtamd.DeviceBuffer(n * 24), rtamd.DeviceBuffer(n * 24), rtamd.DeviceBuffer(n * 24)
-    d_rays.from_host(rays)
-    d_wo.from_host(-rays["d"])
+    # the pixel-centre camera rays (Camera::generate_ray, camera.h) in frame order,
+    # generated on the device; wo = -d needs one read-back of the directions
+    assert rtamd.camera_rays_device(sc, W, H, rtamd.RT_RAYS_CENTRE, None, d_rays) == n
+    d_wo.from_host(-d_rays.to_host(np.uint8).view(rtamd.RAY_DTYPE)["d"])
     st = rtamd.Stats()
     ti, ts, tr = [], [], []
     for k in range(1 + a.reps):   # (one warm-up round)
