@@ -34,6 +34,38 @@ int rt_test_jitter_device(int K_blocks, int64_t q0, int64_t q1, int64_t first, i
 struct rt_scene;
 int rt_test_compile_info(const struct rt_scene* s, int32_t* out);
 
+/* Host-only: a histogram of the compiled forms of a scene (scene_compile.hpp),
+ * which rt_test_compile_info's totals do not tell apart, into
+ * out[0 .. RT_TEST_FORMS_LEN) (cap >= RT_TEST_FORMS_LEN), at these offsets:
+ *   OBJ + k          objects of DevObjKind k (7 kinds, cull headers included)
+ *   CHAIN_CORE + c   OBJ_CHAIN objects with a leaf (0) / compact CSG (1) core
+ *   CHAIN_M + m      OBJ_CHAIN objects under m = 0, 1, 2, >= 3 transforms
+ *   CHAIN_M3_CORE + c  those with m >= 3, by core
+ *   FOLD + op        fold objects (DevObj::nfold > 0) per rt_csg_op
+ *   OP + k           program ops of DevOpCode k (9 codes)
+ *   NEVER_TOP + t    OP_NEVER ops with top = t (0, 1: hit mode; 2: interval mode)
+ *   IVL_GROUP + op   OP_IVL_GROUP headers per rt_csg_op
+ *   RAY_DEPTH, IVL_DEPTH  CompiledScene::max_ray_depth / max_ivl_depth
+ *   BOUNDED          objects (cull headers aside) with a bounding ball
+ *   PREFILTER        OBJ_CHAIN objects with leaf prefilter balls
+ * No device is touched. */
+enum {
+    RT_TEST_FORMS_OBJ = 0,
+    RT_TEST_FORMS_CHAIN_CORE = 7,
+    RT_TEST_FORMS_CHAIN_M = 9,
+    RT_TEST_FORMS_CHAIN_M3_CORE = 13,
+    RT_TEST_FORMS_FOLD = 15,
+    RT_TEST_FORMS_OP = 18,
+    RT_TEST_FORMS_NEVER_TOP = 27,
+    RT_TEST_FORMS_IVL_GROUP = 30,
+    RT_TEST_FORMS_RAY_DEPTH = 33,
+    RT_TEST_FORMS_IVL_DEPTH = 34,
+    RT_TEST_FORMS_BOUNDED = 35,
+    RT_TEST_FORMS_PREFILTER = 36,
+    RT_TEST_FORMS_LEN = 37
+};
+int rt_test_compile_forms(const struct rt_scene* s, int32_t* out, int cap);
+
 /* Host-only: the wave BVH of a scene (CompiledScene::wobjs ...).  counts[2] =
  * {objects in the wave list, chunks} (both 0: no BVH); up to cap_objs
  * entries of worig (each listed object's index in the compiled object table)

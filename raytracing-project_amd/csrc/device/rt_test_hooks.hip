@@ -354,6 +354,36 @@ extern "C" int rt_test_compile_info(const rt_scene* s, int32_t* out) {
     }
 }
 
+extern "C" int rt_test_compile_forms(const rt_scene* s, int32_t* out, int cap) {
+    if (!s || !out || cap < RT_TEST_FORMS_LEN) return RT_ERR_INVALID_ARG;
+    try {
+        const rtamd::CompiledScene cs = rtamd::compile_scene(*rt_scene_get_desc(s));
+        std::fill(out, out + RT_TEST_FORMS_LEN, 0);
+        auto bin3 = [](int v) { return v < 0 ? 0 : v > 2 ? 2 : v; };
+        for (const auto& o : cs.objs) {
+            if (o.kind >= 0 && o.kind <= rtamd::OBJ_GROUP) ++out[RT_TEST_FORMS_OBJ + o.kind];
+            if (o.kind != rtamd::OBJ_GROUP && o.has_bound) ++out[RT_TEST_FORMS_BOUNDED];
+            if (o.kind != rtamd::OBJ_CHAIN) continue;
+            if (o.npb > 0) ++out[RT_TEST_FORMS_PREFILTER];
+            ++out[RT_TEST_FORMS_CHAIN_CORE + (o.core ? 1 : 0)];
+            ++out[RT_TEST_FORMS_CHAIN_M + std::min(o.m, 3)];
+            if (o.m >= 3) ++out[RT_TEST_FORMS_CHAIN_M3_CORE + (o.core ? 1 : 0)];
+            if (o.nfold > 0) ++out[RT_TEST_FORMS_FOLD + bin3(o.fold_op)];
+        }
+        for (const auto& op : cs.ops) {
+            if (op.op >= 0 && op.op <= rtamd::OP_IVL_GROUP) ++out[RT_TEST_FORMS_OP + op.op];
+            if (op.op == rtamd::OP_NEVER) ++out[RT_TEST_FORMS_NEVER_TOP + bin3(op.top)];
+            if (op.op == rtamd::OP_IVL_GROUP) ++out[RT_TEST_FORMS_IVL_GROUP + bin3(op.csg_op)];
+        }
+        out[RT_TEST_FORMS_RAY_DEPTH] = cs.max_ray_depth;
+        out[RT_TEST_FORMS_IVL_DEPTH] = cs.max_ivl_depth;
+        return RT_OK;
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("scene compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+}
+
 // ------------------------------------------------------ frame planners (CPU)
 extern "C" int rt_test_plan_dist(int H, int world, int rank, int mode, int kind, int chunks, int32_t* counts,
                                  int32_t* rows_out, int32_t* bounds_out, int32_t* rowtab_out, int cap_table) {

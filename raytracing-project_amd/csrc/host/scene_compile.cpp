@@ -2,7 +2,8 @@
 //
 // Bounds: every node gets a conservative bounding sphere in the frame of the
 // ray it is queried with, or "unbounded" (half-spaces and anything whose
-// result can extend along them), or "empty" (can never report an interval
+// result can extend along them; the subtree of a Scaling that the reference
+// answers for far from its image, xform_ball), or "empty" (can never report an interval
 // or a hit: degenerate Scaling, transform.cpp:97).  The bound of a CSG node
 // follows from the reference's interval semantics (csg.cpp:61-163): a union
 // is inside only where a child is; an intersection only where BOTH are; a
@@ -25,6 +26,7 @@ struct Bound {
     enum Kind { Empty, Unbounded, Ball } kind = Unbounded;
     double c[3] = {0, 0, 0};
     double r = 0;
+    double aniso = 1;   // Ball: the largest product of max|factor| / min|factor| over the Scalings below (xform_ball)
 };
 
 Bound ball(double x, double y, double z, double r) {
@@ -41,11 +43,11 @@ Bound merge_union(const Bound& a, const Bound& b) {
     if (a.kind == Bound::Unbounded || b.kind == Bound::Unbounded) return Bound{};
     double d[3] = {b.c[0] - a.c[0], b.c[1] - a.c[1], b.c[2] - a.c[2]};
     double dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (dist + b.r <= a.r) return a;
-    if (dist + a.r <= b.r) return b;
+    const double aniso = std::max(a.aniso, b.aniso);
+    Bound o = (dist + b.r <= a.r) ? a : b;
+    o.aniso = aniso;
+    if (dist + b.r <= a.r || dist + a.r <= b.r) return o;
     double R = 0.5 * (dist + a.r + b.r);
-    Bound o;
-    o.kind = Bound::Ball;
     double k = (dist > 0) ? (R - a.r) / dist : 0.0;
     for (int i = 0; i < 3; ++i) o.c[i] = a.c[i] + d[i] * k;
     o.r = R;
@@ -109,18 +111,48 @@ bool is_degenerate_scaling(const rt_node& n) {
            (std::fabs(n.v[0]) < kEPS || std::fabs(n.v[5]) < kEPS || std::fabs(n.v[10]) < kEPS);
 }
 
+// Scalings whose subtree gets no bound (Culling), because the
+// reference's own arithmetic answers for rays that pass far from the subtree's
+// image:
+//  - max|factor| >= 1e6.  The reference divides the unit direction by the
+//    factors and builds a Ray from it (transform.cpp:106-108), and Ray's
+//    constructor replaces a direction of length <= 1e-6 by (0, 1, 0)
+//    (core.h:95-101, 278).  The local direction is at least 1 / max|factor|
+//    long, so this starts at 1e6 (with a margin for the rounding of the
+//    division and the length): the local ray is then no image of the world ray.
+//  - max|factor| / min|factor| > kMaxAniso, multiplied along nested Scalings
+//    (Bound::aniso).  A sphere test cancels |oc|^2 against (oc.d)^2
+//    (geometry.cpp:48-78), so it takes a miss by up to ~2e-8 |oc| for a hit;
+//    in the local frame |oc| is the world distance D / min|factor| and a miss
+//    measured there is up to max|factor| times as long in the world: spurious
+//    hits up to ~2e-8 * aniso * D off the image (measured: 0.017 D at 1e6).
+//    The f32 cull tests leave about 1e-6 D of their 4e-6 margin to the
+//    reference's rounding (rt_device.hpp, f32 culling), which covers an
+//    anisotropy of 16 three times over.
+constexpr double kMaxAniso = 16.0;
+
+double scaling_max(const rt_node& n) { return std::max(std::fabs(n.v[0]), std::max(std::fabs(n.v[5]), std::fabs(n.v[10]))); }
+double scaling_min(const rt_node& n) { return std::min(std::fabs(n.v[0]), std::min(std::fabs(n.v[5]), std::fabs(n.v[10]))); }
+
 // The ball b of a transform node's child, in the node's parent frame.
 Bound xform_ball(const rt_node& n, const Bound& b) {
     if (b.kind != Bound::Ball) return b;
-    if (n.kind == RT_NODE_TRANSLATION) return ball(b.c[0] + n.v[3], b.c[1] + n.v[7], b.c[2] + n.v[11], b.r);
-    if (n.kind == RT_NODE_SCALING) {
-        double s = std::max(std::fabs(n.v[0]), std::max(std::fabs(n.v[5]), std::fabs(n.v[10])));
-        return ball(b.c[0] * n.v[0], b.c[1] * n.v[5], b.c[2] * n.v[10], b.r * s);
+    Bound o;
+    if (n.kind == RT_NODE_TRANSLATION) {
+        o = ball(b.c[0] + n.v[3], b.c[1] + n.v[7], b.c[2] + n.v[11], b.r);
+    } else if (n.kind == RT_NODE_SCALING) {
+        const double s = scaling_max(n);
+        o = ball(b.c[0] * n.v[0], b.c[1] * n.v[5], b.c[2] * n.v[10], b.r * s);
+        o.aniso = b.aniso * (s / scaling_min(n));   // (a degenerate Scaling never comes here)
+        if (s >= 0.999e6 || !(o.aniso <= kMaxAniso)) return Bound{};   // (unbounded)
+        return o;
+    } else {
+        const double* M = n.v;   // rotation
+        o = ball(M[0] * b.c[0] + M[1] * b.c[1] + M[2] * b.c[2] + M[3], M[4] * b.c[0] + M[5] * b.c[1] + M[6] * b.c[2] + M[7],
+                 M[8] * b.c[0] + M[9] * b.c[1] + M[10] * b.c[2] + M[11], b.r);
     }
-    const double* M = n.v;   // rotation
-    return ball(M[0] * b.c[0] + M[1] * b.c[1] + M[2] * b.c[2] + M[3],
-                M[4] * b.c[0] + M[5] * b.c[1] + M[6] * b.c[2] + M[7],
-                M[8] * b.c[0] + M[9] * b.c[1] + M[10] * b.c[2] + M[11], b.r);
+    o.aniso = b.aniso;
+    return o;
 }
 
 class Compiler {
@@ -155,6 +187,7 @@ public:
             if (b.kind != Bound::Ball) return;   // a half-space leaf: no prefilter
             b.r += slop;
             for (size_t k = chain.size(); k-- > 0;) b = xform_ball(d_.nodes[chain[k]], b);
+            if (b.kind != Bound::Ball) return;   // a Scaling without a bound in the chain (xform_ball): no world ball
             float fb[4];
             float_ball(b.c, b.r, fb);
             balls.insert(balls.end(), fb, fb + 4);

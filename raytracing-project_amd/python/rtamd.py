@@ -507,6 +507,34 @@ def kernel_name(scene: Scene, mode: int, flags: int = RT_FLAG_NONE) -> tuple[int
     return rc, buf.value.decode()
 
 
+OBJ_KINDS = ("sphere", "half", "poke", "chain", "eager", "never", "group")
+OP_CODES = ("xpush", "leaf_ivl", "csg", "xpop_ivl", "leaf_isect", "csg_isect", "xpop_hit", "never", "ivl_group")
+CSG_OPS = ("union", "intersection", "difference")
+
+
+def compile_forms(scene: Scene) -> dict:
+    """rt_test_compile_forms: the histogram of a scene's compiled forms
+    (include/rt_test.h), as {"obj/<kind>", "chain_core/leaf|csg",
+    "chain_m/0|1|2|3+", "chain_m3+/leaf|csg", "fold/<op>", "op/<code>",
+    "never_top/0|1|2", "ivl_group/<op>", "max_ray_depth", "max_ivl_depth",
+    "bounded", "prefilter"}.
+    Host only."""
+    lib = amd_lib()
+    lib.rt_test_compile_forms.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
+    n = 37   # RT_TEST_FORMS_LEN
+    out = (C.c_int32 * n)()
+    rc = lib.rt_test_compile_forms(scene.handle, out, n)
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    keys = ([f"obj/{k}" for k in OBJ_KINDS] + ["chain_core/leaf", "chain_core/csg"] +
+            [f"chain_m/{m}" for m in ("0", "1", "2", "3+")] + ["chain_m3+/leaf", "chain_m3+/csg"] +
+            [f"fold/{o}" for o in CSG_OPS] + [f"op/{k}" for k in OP_CODES] +
+            [f"never_top/{t}" for t in (0, 1, 2)] + [f"ivl_group/{o}" for o in CSG_OPS] +
+            ["max_ray_depth", "max_ivl_depth", "bounded", "prefilter"])
+    assert len(keys) == n
+    return dict(zip(keys, (int(v) for v in out)))
+
+
 KERNEL_TABLES = ("rtd std", "rtd paper", "rtf std", "rtf paper", "rtdb std", "rtdb paper", "rtd query", "rtdb query",
                  "finish")
 

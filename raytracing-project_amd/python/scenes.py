@@ -561,6 +561,271 @@ def crowd_scene(seed: int, n_objects: int = 150, dpi: int = 16) -> dict:
     return _base(objs, recursion=3, dpi=dpi, lights=lights)
 
 
+# ------------------------------------------------------- scene-graph scenes
+def _tr(f, sub):
+    return {"translation": {"factors": [float(v) for v in f], "subject": sub}}
+
+
+def _sc(f, sub):
+    return {"scaling": {"factors": [float(v) for v in f], "subject": sub}}
+
+
+def _rot(angle, axis, sub):
+    return {"rotation": {"angle": angle, "direction": axis, "subject": sub}}
+
+
+def _half(p, n, col):
+    return {"halfSpace": {"position": [float(v) for v in p], "normal": [float(v) for v in n], "color": col}}
+
+
+GRAPH_NULL_CENTRE = [-0.9, 0.0, -1.0]
+
+
+def graph_cases(dpi: int = 24) -> dict[str, dict]:
+    """Hand-written scenes for the compiled object forms and the scene shapes
+    no other family has (scene_compile.cpp; tests/test_graph_scenes.py,
+    tests/test_gpu_graph.py), each over a floor or another hit surface:
+      never_top        a degenerate Scaling (a factor below 1e-6,
+                       transform.cpp:103) as a top-level object: OBJ_NEVER
+      never_in_csg     that subtree as the right operand of a union, a
+                       difference and an intersection and as the left operand
+                       of a difference (OP_NEVER in interval mode; an Empty
+                       bound on either side of every operator)
+      never_mid_chain  translation(scaling [1, 0, 1](rotation(sphere)))
+      neg_scale        mirrors: negative factors over a sphere, a pokeball
+                       (its button direction mirrored) and a difference
+      big_scale_fallback  scaling [2e6] * 3: the local direction is shorter
+                       than 1e-6 and Ray's constructor replaces it by
+                       (0, 1, 0) (core.h:278), so the local ray is no image of
+                       the world ray and no bound of the subtree holds
+      scale_1e5        factors 1e5 over a sphere of radius 6e-6, 1e-5 over one
+                       of radius 5e4
+      scale_threshold  factor 1e-6 (not degenerate: a disc 1.6e-6 thick seen
+                       from the side) and 0.99e-6 (degenerate)
+      rot_right_angles rotations by 90, 180, 360, -450 and 0 degrees
+      xform_half       transforms directly over half-spaces (unbounded chains)
+      csg_self         union, intersection and difference of a sphere with
+                       itself: every event a tie of the event order
+      csg_concentric_tangent  a shell, externally tangent spheres, a disjoint
+                       intersection, a small sphere minus one that encloses it
+      csg_unbounded    a slab of two half-spaces, a wall minus a sphere
+      mixed_deep       CSG of other operators under CSG, transforms inside
+                       operands and over the whole
+      null_mat_eager   a union with a leaf that has no material (graph_load
+                       removes it): a non-compact core, so an eager program"""
+    floor = _floor()
+    sc = {}
+
+    def put(name, objs):
+        sc[name] = _base(objs, recursion=3, dpi=dpi)
+
+    def deg():
+        return _sc([1e-7, 1, 1], _sph([0, 0, 0], 0.5, _mat([0.9, 0.1, 0.9])))
+
+    put("never_top", [floor, _sc([1e-7, 1, 1], _sph([-0.8, 0.0, -1.0], 0.6, _mat([0.9, 0.1, 0.9]))),
+                      _sph([0.8, 0.0, -1.5], 0.6, _mat([0.2, 0.5, 0.9]))])
+    put("never_in_csg", [
+        floor,
+        _tr([-1.5, 0.0, -1.0], {"union": [_sph([0, 0, 0], 0.5, _mat([0.9, 0.3, 0.2])), deg()]}),
+        _tr([-0.3, 0.2, -1.5], {"difference": [_sph([0, 0, 0], 0.6, _mat([0.3, 0.9, 0.2])), deg()]}),
+        _tr([0.9, 0.0, -1.0], {"intersection": [_sph([0, 0, 0], 0.5, _mat([0.2, 0.3, 0.9])), deg()]}),
+        {"difference": [_tr([1.7, 0.5, -1.0], deg()), _sph([1.7, 0.5, -1.0], 0.4, _mat([0.9, 0.9, 0.2]))]},
+        _sph([1.6, -0.5, -0.5], 0.4, _mat([0.2, 0.8, 0.8], reflected=[0.4, 0.4, 0.4])),
+    ])
+    put("never_mid_chain", [
+        floor,
+        _tr([-0.8, 0.0, -1.0], _sc([1, 0, 1], _rot(30, 1, _sph([0, 0, 0], 0.6, _mat([0.9, 0.1, 0.9]))))),
+        _sph([0.8, 0.0, -1.5], 0.6, _mat([0.8, 0.6, 0.2], reflected=[0.3, 0.3, 0.3]))])
+    put("neg_scale", [
+        floor,
+        _sc([-1.5, 1, 1], _sph([0.9, 0.1, -1.5], 0.5, _mat([0.9, 0.3, 0.2], reflected=[0.3, 0.3, 0.3]))),
+        _sc([1, -1, -0.8], {"pokeball": {"position": [0.0, -0.3, 1.5], "radius": 0.5, "button_dir": [0.3, -0.2, -1.0]}}),
+        _sc([-1, -1, -1], {"difference": [
+            _sph([-1.3, -0.2, 1.2], 0.6, _mat([0.3, 0.4, 0.9], refracted=[0.5, 0.5, 0.5]), index=1.5),
+            _sph([-1.3, -0.4, 0.7], 0.4, _mat([0.9, 0.9, 0.2]))]})])
+    put("big_scale_fallback", [floor, _sc([2e6, 2e6, 2e6], _sph([0, 0.5, 0], 0.4, _mat([0.9, 0.5, 0.1]))),
+                               _sph([1.2, 0.0, -1.5], 0.6, _mat([0.2, 0.5, 0.9]))])
+    put("scale_1e5", [
+        floor,
+        _sc([1e5] * 3, _sph([-1e-5, 0.0, -1.2e-5], 6e-6, _mat([0.9, 0.3, 0.2]))),
+        _sc([1e-5] * 3, _sph([1e5, 0.0, -1.5e5], 5e4, _mat([0.2, 0.5, 0.9], reflected=[0.3, 0.3, 0.3])))])
+    put("scale_threshold", [
+        floor,
+        _sc([1e-6, 1, 1], _sph([1e6, 0.0, 1.5], 0.8, _mat([0.9, 0.3, 0.2]))),
+        _sc([0.99e-6, 1, 1], _sph([-1e6 / 0.99, 0.0, 1.5], 0.8, _mat([0.9, 0.1, 0.9]))),
+        _sph([0.0, -0.3, -1.5], 0.7, _mat([0.2, 0.5, 0.9]))])
+    put("rot_right_angles", [
+        floor,
+        _rot(90, 0, _sph([-1.4, 1.0, -0.8], 0.45, _mat([0.9, 0.3, 0.2]))),               # -> (-1.4, 0.8, 1.0)
+        _rot(180, 1, _sph([-1.0, -0.4, 1.5], 0.5, _mat([0.3, 0.9, 0.2]))),               # -> (1.0, -0.4, -1.5)
+        _rot(360, 2, _sph([0.0, 0.9, -2.0], 0.5, _mat([0.2, 0.3, 0.9], reflected=[0.4, 0.4, 0.4]))),
+        _rot(-450, 2, {"pokeball": {"position": [0.5, -0.9, -1.0], "radius": 0.45, "button_dir": [0.2, 0.1, 1.0]}}),
+        _rot(0, 1, _tr([0, 0, 0], _sph([1.5, 0.7, -1.0], 0.4, _mat([0.9, 0.9, 0.2]))))])
+    put("xform_half", [
+        _rot(8, 2, _floor()),
+        _sc([1, 2, 0.5], _half([0, 0, -12], [0, 0, 1], _mat([0.5, 0.5, 0.7]))),
+        _tr([0.5, 0, 0], _sc([-1, 1, 1], _half([2.7, 0, 0], [-1, 0, 0.2], _mat([0.7, 0.5, 0.5])))),
+        _sph([0.3, 0.0, -1.5], 0.7, _mat([0.2, 0.7, 0.4], reflected=[0.3, 0.3, 0.3]))])
+
+    def same(c, r, col):
+        return [_sph(c, r, _mat(col)), _sph(c, r, _mat(col))]
+
+    put("csg_self", [floor, {"union": same([-1.4, 0.0, -1.0], 0.6, [0.9, 0.3, 0.2])},
+                     {"intersection": same([0.0, 0.2, -1.5], 0.6, [0.3, 0.9, 0.2])},
+                     {"difference": same([1.4, 0.0, -1.0], 0.6, [0.2, 0.3, 0.9])}])
+    put("csg_concentric_tangent", [
+        floor,
+        {"difference": [_sph([-1.3, 0.0, -1.0], 0.6, _mat([0.9, 0.3, 0.2], refracted=[0.6, 0.6, 0.6]), index=1.3),
+                        _sph([-1.3, 0.0, -1.0], 0.4, _mat([0.2, 0.9, 0.3]))]},
+        {"union": [_sph([0.0, 0.3, -1.5], 0.4, _mat([0.3, 0.3, 0.9])), _sph([0.8, 0.3, -1.5], 0.4, _mat([0.9, 0.9, 0.2]))]},
+        {"intersection": [_sph([1.6, -0.5, -0.6], 0.3, _mat([0.9, 0.1, 0.9])),
+                          _sph([1.6, 0.9, -0.6], 0.3, _mat([0.9, 0.1, 0.9]))]},
+        {"difference": [_sph([-0.3, -0.6, -0.3], 0.2, _mat([0.9, 0.1, 0.9])),
+                        _sph([-0.3, -0.6, -0.3], 0.5, _mat([0.9, 0.1, 0.9]))]}])
+    put("csg_unbounded", [
+        # (a half-space is solid on the side its normal points to)
+        {"intersection": [_half([0, -1.0, 0], [0, -1, 0], _mat([0.5, 0.6, 0.5])),
+                          _half([0, -1.4, 0], [0, 1, 0], _mat([0.6, 0.5, 0.5]))]},
+        {"difference": [_half([0, 0, -5], [0, 0, -1], _mat([0.5, 0.5, 0.7])),
+                        _sph([0.0, 0.3, -5.0], 1.2, _mat([0.9, 0.6, 0.2]))]},
+        _sph([1.2, -0.3, -1.5], 0.6, _mat([0.2, 0.5, 0.9], reflected=[0.3, 0.3, 0.3]))])
+    put("mixed_deep", [
+        floor,
+        {"difference": [
+            {"union": [_sph([-1.1, 0.1, -1.2], 0.6, _mat([0.9, 0.3, 0.2])),
+                       _rot(40, 2, _sc([1.5, 0.6, 1.0], _sph([-0.35, 0.55, -1.2], 0.45, _mat([0.3, 0.9, 0.2]))))]},
+            {"intersection": [_tr([-0.9, 0.2, -0.6], {"pokeball": {"position": [0, 0, 0], "radius": 0.45,
+                                                                   "button_dir": [0.1, 0.2, 1.0]}}),
+                              _half([0, 0.1, 0], [0, -1, 0], _mat([0.8, 0.8, 0.8]))]}]},
+        _tr([1.2, 0.1, -1.3], _rot(25, 1, {"csg": {
+            "operator": "intersection",
+            "left": {"union": [_sph([-0.25, 0, 0], 0.5, _mat([0.2, 0.3, 0.9])),
+                               _sph([0.25, 0, 0], 0.5, _mat([0.9, 0.9, 0.2], reflected=[0.3, 0.3, 0.3]))]},
+            "right": {"difference": [_sph([0, 0.1, 0], 0.6, _mat([0.9, 0.2, 0.7])),
+                                     _sph([0, 0.2, 0.5], 0.3, _mat([0.2, 0.9, 0.9]))]}}}))])
+    put("null_mat_eager", [
+        floor,
+        {"union": [_sph(GRAPH_NULL_CENTRE, 0.6, _mat([0.5, 0.5, 0.5])),
+                   _sph([-0.3, 0.3, -1.2], 0.5, _mat([0.3, 0.8, 0.3]))]},
+        _sph([1.1, 0.0, -1.5], 0.6, _mat([0.2, 0.3, 0.4], reflected=[0.6, 0.6, 0.6]))])
+    return sc
+
+
+GRAPH_EAGER_CASES = ("never_in_csg", "mixed_deep", "null_mat_eager")
+# the named cases with a transform or a never-hit form (the radiance tests)
+GRAPH_XFORM_CASES = ("never_top", "never_in_csg", "never_mid_chain", "neg_scale", "big_scale_fallback", "scale_1e5",
+                     "scale_threshold", "rot_right_angles", "xform_half", "mixed_deep")
+
+
+def graph_load(rt, name: str, scene: dict):
+    """graph_cases()[name] (or a graph_scene) as a loaded scene: null_mat_eager
+    loses the material of the sphere at GRAPH_NULL_CENTRE, which the JSON
+    schema cannot spell (rt = the rtamd module)."""
+    sc = rt.load_scene_from_json_text(json.dumps(scene))
+    if name == "null_mat_eager":
+        sc = rt.with_null_materials(sc, rt.sphere_nodes_at(sc, [GRAPH_NULL_CENTRE]))
+    return sc
+
+
+# Transform parameters of graph_scene: scaling factor triples (mirrors, factors
+# down to 1e-3 and up to 1e3, degenerate ones last) and rotation angles.
+_GRAPH_FACTORS = ([-1, 1, 1], [1, -1, 1], [-1, -1, -1], [0.5, 2, 1], [1.3, 0.7, 1.0], [2, 0.5, -1.5], [1e-3, 1e-3, 1e-3],
+                  [1e3, 1e3, 1e3], [-40, 40, 40], [0.02, 0.05, 0.02], [1, 1, 1], [0.8, 0.8, 1.25])
+_GRAPH_DEGENERATE = ([1, 0, 1], [1e-7, 1, 1], [1, 1, -5e-7])
+_GRAPH_ANGLES = (0, 90, 180, 270, 360, -90, 450, -450, 30, -45, 60, 137.5, 1e-9)
+
+
+def graph_scene(seed: int, dpi: int = 16) -> dict:
+    """A seeded random scene graph: about 10 top-level objects over a floor,
+    each a recursive choice (depth up to 4) among sphere, pokeball,
+    translation, rotation, scaling and the three CSG operators (n-ary arrays
+    or a binary csg node) with operands of any kind - a CSG of another
+    operator, a transform inside an operand, a half-space as the last operand
+    of a difference or an intersection (never of a union, as crowd_scene
+    explains).  Transform parameters come from _GRAPH_FACTORS / _GRAPH_ANGLES,
+    now and then a degenerate factor.  A node is built around the point and
+    size it should have in its parent's frame, so that every object stays in
+    view whatever stands above it.  Lights and materials as crowd_scene."""
+    import random
+    rnd = random.Random(seed)
+
+    def col():
+        m = _mat([rnd.random(), rnd.random(), rnd.random()], shininess=rnd.choice([4, 8, 16, 32]))
+        u = rnd.random()
+        if u < 0.12:
+            m["reflected"] = [0.5, 0.5, 0.5]
+        elif u < 0.2:
+            m["refracted"] = [0.6, 0.6, 0.6]
+        return m
+
+    def leaf(c, r):
+        if rnd.random() < 0.25:
+            return {"pokeball": {"position": list(c), "radius": r,
+                                 "button_dir": [rnd.uniform(-1, 1), rnd.uniform(-1, 1), 1.0]}}
+        return {"sphere": {"position": list(c), "radius": r, "color": col(), "index": rnd.choice([1.0, 1.33, 1.5])}}
+
+    def near(c, r, k=0.6):
+        return [c[i] + rnd.uniform(-k, k) * r for i in range(3)]
+
+    def xform(c, r, depth):
+        k = rnd.randint(0, 2)
+        if k == 0:
+            f = [rnd.uniform(-1.5, 1.5) * rnd.choice([0, 1, 1]) for _ in range(3)]
+            return _tr(f, node([c[i] - f[i] for i in range(3)], r, depth - 1))
+        if k == 1:
+            ang, ax = rnd.choice(_GRAPH_ANGLES), rnd.randint(0, 2)
+            a = -math.radians(ang)
+            i, j = [(1, 2), (2, 0), (0, 1)][ax]
+            q = list(c)
+            q[i] = math.cos(a) * c[i] - math.sin(a) * c[j]
+            q[j] = math.sin(a) * c[i] + math.cos(a) * c[j]
+            return _rot(ang, ax, node(q, r, depth - 1))
+        if rnd.random() < 0.06:
+            return _sc(rnd.choice(_GRAPH_DEGENERATE), node(c, r, depth - 1))
+        f = rnd.choice(_GRAPH_FACTORS)
+        g = abs(f[0] * f[1] * f[2]) ** (1.0 / 3.0)
+        return _sc(f, node([c[i] / f[i] for i in range(3)], r / g, depth - 1))
+
+    def csg(c, r, depth):
+        op = rnd.choice(["union", "union", "difference", "intersection"])
+        n = rnd.choice([2, 2, 3, 4, 6])
+        # a union's operands spread out, the others overlap the first
+        spread = 0.8 if op == "union" else 0.45
+        kids = [node(near(c, r, 0.3), 0.75 * r, depth - 1)]
+        kids += [node(near(c, r, spread), rnd.uniform(0.35, 0.7) * r, depth - 1 if rnd.random() < 0.5 else 0)
+                 for _ in range(n - 1)]
+        if op != "union" and rnd.random() < 0.3:
+            kids.append(_half(near(c, r, 0.3), [rnd.uniform(-1, 1), 1.0, rnd.uniform(-1, 1)], col()))
+        if rnd.random() < 0.35:
+            rest = kids[1:]
+            right = rest[0] if len(rest) == 1 else {rnd.choice(["union", "union", "intersection"])
+                                                    if op != "union" else "union": rest}
+            if "halfSpace" in rest[-1] and len(rest) > 1:
+                # (the half-space stays the last operand of its own operator)
+                right = {op if op == "intersection" else "union": rest[:-1]}
+                return {"csg": {"operator": op, "left": {"csg": {"operator": op, "left": kids[0], "right": right}},
+                                "right": rest[-1]}}
+            return {"csg": {"operator": op, "left": kids[0], "right": right}}
+        return {op: kids}
+
+    def node(c, r, depth):
+        u = rnd.random()
+        if depth <= 0 or u < 0.2:
+            return leaf(c, r)
+        if u < 0.6:
+            return xform(c, r, depth)
+        return csg(c, r, depth)
+
+    objs = [{"halfSpace": {"position": [0, -1.3, 0], "normal": [0, 1, 0], "color": col()}}]
+    for k in range(10):
+        c = [-2.4 + 1.2 * (k % 5) + rnd.uniform(-0.2, 0.2), rnd.uniform(-0.6, 1.2), -1.0 - 1.6 * (k // 5)
+             + rnd.uniform(-0.3, 0.3)]
+        objs.append(node(c, rnd.uniform(0.35, 0.6), rnd.randint(1, 4)))
+    lights = [{"position": [rnd.uniform(-6, 6), rnd.uniform(3, 7), rnd.uniform(-2, 6)],
+               "intensity": [rnd.uniform(8, 25)] * 3} for _ in range(4)]
+    return _base(objs, recursion=3, dpi=dpi, lights=lights)
+
+
 # ------------------------------------------------------------ shading scenes
 SHADING_LAYOUTS = ("few", "wave", "csg", "xform", "bvh")
 SHADING_EXPONENTS = (0, 1, 2, 3, 5, 7, 127, 255, 1000, 1023, 1024, 2000, 12.5, 0.5, -2)

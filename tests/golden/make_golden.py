@@ -28,8 +28,12 @@ turned into IR by our loader (librt_host.so).  Outputs are data only:
                specular exponents, extreme coefficients, a non-vacuum medium,
                null materials), both modes, with each scene's JSON and the
                nodes / materials patched through the IR
+  graph.npz    frames + counts of the scene-graph scenes (scenes.graph_cases,
+               scenes.graph_scene at GRAPH_SEEDS), both modes, at GRAPH_DPI,
+               and intersect / interval answers of every top-level object of
+               the named cases for 64 rays per case
 
-Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh shading]
+Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh shading graph]
 """
 from __future__ import annotations
 
@@ -277,6 +281,58 @@ def make_shading():
     print("shading:", len(data))
 
 
+GRAPH_SEEDS = (2, 3, 8, 9, 10, 12)
+GRAPH_DPI = 12   # 48 x 36 frames: the file stays under 1 MB
+
+
+def graph_golden_scenes(dpi=GRAPH_DPI) -> dict[str, dict]:
+    out = dict(scenes.graph_cases(dpi=dpi))
+    for seed in GRAPH_SEEDS:
+        out[f"seed{seed}"] = scenes.graph_scene(seed, dpi=dpi)
+    return out
+
+
+def make_graph():
+    """The scene-graph scenes (scenes.graph_cases, scenes.graph_scene), both
+    modes, and the named cases' top-level objects ray by ray (rows of misses
+    are stored as zeros)."""
+    lib = rtamd.ref_lib()
+    rng = np.random.default_rng(4321)
+    data = {"dpi": np.array(GRAPH_DPI, dtype=np.int64), "seeds": np.array(GRAPH_SEEDS, dtype=np.int64)}
+    named = set(scenes.graph_cases())
+    for name, d in graph_golden_scenes().items():
+        sc = scenes.graph_load(rtamd, name, d)
+        for mode in (0, 1):
+            with quiet_stdout():
+                fb, ni, no = rtamd.ref_render(sc, sc.width, sc.height, mode)
+            data[f"{name}/{mode}/fb"] = fb
+            data[f"{name}/{mode}/counts"] = np.array([ni, no], dtype=np.int64)
+        if name not in named:
+            continue
+        n = 64
+        o, dirs = _random_rays(rng, n, np.array([0.0, 0.0, -1.2]), 1.5)
+        data[f"{name}/o"], data[f"{name}/d"] = o, dirs
+        for k in range(sc.desc.n_objects):
+            node = int(sc.desc.objects[k])
+            ok = (C.c_int * n)()
+            hits = (rtamd.OracleHit * n)()
+            lib.ref_node_intersect_batch(sc.desc_ptr, node, n, o.ctypes.data_as(_dp), dirs.ctypes.data_as(_dp),
+                                         1e-4, np.inf, ok, hits)
+            okv = np.array(ok[:], dtype=np.int8)
+            data[f"{name}/{k}/isect/ok"] = okv
+            data[f"{name}/{k}/isect/hit"] = np.where(okv[:, None] != 0, _hits_array(hits), 0.0)
+            t0, t1 = np.zeros(n), np.zeros(n)
+            h0, h1 = (rtamd.OracleHit * n)(), (rtamd.OracleHit * n)()
+            lib.ref_node_interval_batch(sc.desc_ptr, node, n, o.ctypes.data_as(_dp), dirs.ctypes.data_as(_dp), ok,
+                                        t0.ctypes.data_as(_dp), t1.ctypes.data_as(_dp), h0, h1)
+            okv = np.array(ok[:], dtype=np.int8)
+            data[f"{name}/{k}/ivl/ok"] = okv
+            data[f"{name}/{k}/ivl/rec"] = np.where(okv[:, None] != 0, np.concatenate(
+                [np.stack([t0, t1], axis=1), _hits_array(h0), _hits_array(h1)], axis=1), 0.0)
+    np.savez_compressed(os.path.join(HERE, "graph.npz"), **data)
+    print("graph:", len(data))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         for what in sys.argv[1:]:
@@ -291,3 +347,4 @@ if __name__ == "__main__":
     make_crowd()
     make_bvh()
     make_shading()
+    make_graph()

@@ -54,9 +54,13 @@ class Case:
     def __init__(self, rt, name):
         text, lights = SCENES[name]
         sc = rt.load_scene_from_json_text(text)
-        self.scene = rt.with_dir_lights(sc, lights) if lights else sc
+        self._build(rt, rt.with_dir_lights(sc, lights) if lights else sc, SEED + sorted(SCENES).index(name), name)
+
+    def _build(self, rt, scene, seed, name=""):
+        """The ray recipe on a loaded scene (for the scene families of other files)."""
+        self.scene = scene
         self.rt, self.olib, self.desc = rt, rt.oracle_lib(), self.scene.desc_ptr
-        rng = np.random.default_rng(SEED + sorted(SCENES).index(name))
+        rng = np.random.default_rng(seed)
         W, H = self.scene.width, self.scene.height
         # pixel-centre camera rays (Camera::generate_ray) at random pixels
         cam_o, cam_d = np.empty((N_CAM, 3)), np.empty((N_CAM, 3))
