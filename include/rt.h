@@ -398,7 +398,20 @@ int rt_framebuffer_to_rgb8_device(const double* fb_dev, size_t n_pixels,
  * world units along the normalised direction; tmax may be +inf.  The closest
  * hit applies each object's own accept rule with the tightening tmax, so ties
  * resolve exactly as in the reference; occluded is "any object's intersect in
- * [tmin, tmax]".  FP64, the parity path; the scene's camera plays no part. */
+ * [tmin, tmax]".  FP64, the parity path; the scene's camera plays no part.
+ *
+ * Non-finite rays.  A ray with a NaN or an infinity in o, d, tmin or tmax (or
+ * a d whose length overflows or underflows) is no error: it gets the
+ * reference's own result for that ray, which follows from the reference's
+ * comparisons all being false on a NaN.  That result may be a hit with
+ * t = NaN (a NaN or infinite origin, or an infinite direction, "hits" every
+ * sphere and keeps the last object's record: t, p, n NaN, front_face 0,
+ * occluded 1); a NaN direction, or one of length <= 1e-6, is (0, 1, 0), one
+ * of infinite length the zero vector; tmin = NaN rejects nothing on a leaf.
+ * Such a ray affects no other ray of the batch: every other ray's record is
+ * the bytes it has in a batch without it, with and without RT_FLAG_NO_CULL.
+ * The same holds for rt_query_radiance's rays and for rt_query_shade's hits
+ * and wo under hit_mask = 1 (tests/test_gpu_leaves.py). */
 typedef struct rt_ray {        /* 64 B */
     double o[3];
     double d[3];

@@ -902,6 +902,19 @@ int oracle_scene_occluded_batch(const rt_scene_desc* d, int n, const double* o, 
     return 0;
 }
 
+int oracle_trace_rays(const rt_scene_desc* d, int n, const double* o, const double* dir, double* rgb,
+                      uint64_t* n_isect, uint64_t* n_occl) {
+    for (int i = 0; i < n; ++i) {
+        Ctx c; memset(&c, 0, sizeof(c)); c.s = d;
+        Ray r = make_ray(vget(o + 3 * i), vget(dir + 3 * i));
+        V3 col = trace_recursive(&c, &r, 0);
+        rgb[3 * i] = col.x; rgb[3 * i + 1] = col.y; rgb[3 * i + 2] = col.z;
+        n_isect[i] = c.st.rays_intersect;
+        n_occl[i] = c.st.rays_occluded;
+    }
+    return 0;
+}
+
 int oracle_primary_hits(const rt_scene_desc* d, int W, int H, double* dirs, oracle_hit* hits, uint8_t* ok) {
     for (int j = 0; j < H; ++j)
         for (int i = 0; i < W; ++i) {

@@ -59,6 +59,12 @@ int oracle_scene_occluded(const rt_scene_desc* d, const double o[3], const doubl
 /* oracle_scene_occluded for n rays (o, dir: 3n doubles; tmin, tmax: n). */
 int oracle_scene_occluded_batch(const rt_scene_desc* d, int n, const double* o, const double* dir, const double* tmin,
                                 const double* tmax, uint8_t* out);
+/* Tracer::trace (tracer.cpp:12-14) of Ray(o, dir) for n rays: rgb (3n) and each
+ * ray's own Scene::intersect / Scene::occluded calls.  The ray is built once,
+ * by the Ray constructor, so non-finite components arrive as they are (a ray
+ * that goes through the camera is normalised twice). */
+int oracle_trace_rays(const rt_scene_desc* d, int n, const double* o, const double* dir, double* rgb,
+                      uint64_t* n_isect, uint64_t* n_occl);
 /* The pixel-centre primary hit of every pixel of the W x H frame, pixel (i, j)
  * at index j*W + i: Camera::generate_ray(i, j) -> dirs, Scene::intersect(r,
  * 1e-4, inf) -> ok, hits. */

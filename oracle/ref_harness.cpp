@@ -20,6 +20,7 @@
 #include "csg.h"
 #include "geometry.h"
 #include "scene.h"
+#include "shading.h"
 #include "tracer.h"
 #include "transform.h"
 
@@ -245,6 +246,71 @@ int ref_node_interval_batch(const rt_scene_desc* d, int node, int n, const doubl
         t1[i] = x1;
         export_hit(*b, a, &h0[i]);
         export_hit(*b, c, &h1[i]);
+    }
+    return 0;
+}
+
+// Scene::intersect / Scene::occluded (scene.cpp:10-42) of caller-given rays on
+// the built scene, each ray with its own range; a ray's components may be
+// non-finite (tests/test_leaf_scenes.py pins the oracle to what this returns).
+int ref_scene_intersect_batch(const rt_scene_desc* d, int n, const double* o, const double* dir, const double* tmin,
+                              const double* tmax, int* ok, oracle_hit* out) {
+    auto b = build(d);
+    for (int i = 0; i < n; ++i) {
+        Ray r(Point3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), Dir3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]));
+        Hit h;
+        ok[i] = b->scene.intersect(r, tmin[i], tmax[i], h) ? 1 : 0;
+        export_hit(*b, h, &out[i]);
+    }
+    return 0;
+}
+
+int ref_scene_occluded_batch(const rt_scene_desc* d, int n, const double* o, const double* dir, const double* tmin,
+                             const double* tmax, int* ok) {
+    auto b = build(d);
+    for (int i = 0; i < n; ++i) {
+        Ray r(Point3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), Dir3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]));
+        ok[i] = b->scene.occluded(r, tmin[i], tmax[i]) ? 1 : 0;
+    }
+    return 0;
+}
+
+// Tracer::trace (tracer.cpp:12-14) of Ray(o, dir) for a batch: the colour and
+// the Scene::intersect / Scene::occluded calls of each ray.
+int ref_trace_batch(const rt_scene_desc* d, int n, const double* o, const double* dir, double* rgb, uint64_t* n_isect,
+                    uint64_t* n_occl) {
+    auto b = build(d);
+    Tracer t;
+    t.scene = &b->scene;
+    t.camera = &b->cam;
+    for (int i = 0; i < n; ++i) {
+        Ray r(Point3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), Dir3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]));
+        g_n_isect = g_n_occl = 0;
+        const Color c = t.trace(r);
+        rgb[3 * i + 0] = c.r; rgb[3 * i + 1] = c.g; rgb[3 * i + 2] = c.b;
+        n_isect[i] = g_n_isect;
+        n_occl[i] = g_n_occl;
+    }
+    return 0;
+}
+
+// shade_lambert_phong (shading.cpp:31-138) of caller-given hits (t, p, n, mat
+// as an IR material index; outside the table: a null material) and view
+// directions: the colour and the Scene::occluded calls of each.
+int ref_shade_batch(const rt_scene_desc* d, int n, const oracle_hit* hits, const double* wo, double* rgb,
+                    uint64_t* n_occl) {
+    auto b = build(d);
+    for (int i = 0; i < n; ++i) {
+        Hit h;
+        h.t = hits[i].t;
+        h.p = Point3(hits[i].p[0], hits[i].p[1], hits[i].p[2]);
+        h.n = Dir3(hits[i].n[0], hits[i].n[1], hits[i].n[2]);
+        h.mat = (hits[i].mat >= 0 && hits[i].mat < d->n_materials) ? b->mats[hits[i].mat].get() : nullptr;
+        h.front_face = hits[i].front_face != 0;
+        g_n_occl = 0;
+        const Color c = shade_lambert_phong(b->scene, h, Dir3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]));
+        rgb[3 * i + 0] = c.r; rgb[3 * i + 1] = c.g; rgb[3 * i + 2] = c.b;
+        n_occl[i] = g_n_occl;
     }
     return 0;
 }

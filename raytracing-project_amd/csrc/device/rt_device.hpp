@@ -2712,10 +2712,30 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
 // kept out of line: inlined, its temporaries set the trace kernel's register
 // peak and made the compiler spill ~130 B/lane on the common integer path.
 __device__ __attribute__((noinline)) double pow_general(double x, double y) { return pow(x, y); }
+// RT_POW_ANY_X gives pow_spec a second body under the same name in the
+// translation units that set it.  That is sound only as built here: every
+// caller inlines it (forceinline) and each .hip file is its own device code
+// object (no -fgpu-rdc), so no two bodies ever meet in one link.  A build with
+// relocatable device code has to turn the macro into a template argument.
+// rt_test_pow_spec lives in the trace kernels' unit and tests the body without
+// the comparison; the one with it is tested through rt_query_shade
+// (tests/test_gpu_leaves.py: wo x10, 1e200 and +-inf).
+#ifndef RT_POW_ANY_X
+#define RT_POW_ANY_X 0
+#endif
 
 __device__ __forceinline__ double pow_spec(double x, double y) {
     const int k = (int)y;
-    if (!(y >= 0.0 && y < 1024.0 && (double)k == y)) return pow_general(x, y);
+    // RT_POW_ANY_X (the shading-query builds, rt_shade_*.hip): only |x| <= 2
+    // is powered here, where x^k stays finite.  Once a
+    // product overflows, the low word is inf - inf and the sum NaN where pow
+    // gives +-inf.  r.wo is at most 1 for the tracer's own unit wo, so the
+    // trace kernels do without the comparison (it cost the benchmark frame
+    // 0.028 ms, profiles/leaf_edges/ab.txt); rt_query_shade's caller may hand
+    // in any wo (an infinite one, or 1e200 long), and those powers are the
+    // library's.
+    if (!(y >= 0.0 && y < 1024.0 && (double)k == y && (!RT_POW_ANY_X || __builtin_fabs(x) <= 2.0)))
+        return pow_general(x, y);
     if (k == 0) return 1.0;   // pow(x, 0) = 1 for every x
     // (h, l): an unnormalised double-double (h the rounded product, l the
     // exact product error by fma plus the cross term), 4 / 3 operations per

@@ -4,5 +4,6 @@
 #define RT_NS rtdb
 #define RT_BIG_STACKS 1
 #define RT_GENERAL_ONLY 1
+#define RT_POW_ANY_X 1   // a caller-given wo need not be unit: pow_spec (rt_device.hpp)
 #include "rt_device.hpp"
 #include "rt_shade_kernels.hpp"

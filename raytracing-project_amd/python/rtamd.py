@@ -1331,6 +1331,97 @@ def ref_render(scene: Scene, width: int, height: int, mode: int):
     return fb, int(ni.value), int(no.value)
 
 
+def _ray_args(rays):
+    rays = np.asarray(rays, dtype=RAY_DTYPE)
+    cols = [np.ascontiguousarray(rays[f], dtype=np.float64) for f in ("o", "d", "tmin", "tmax")]
+    return len(rays), cols, [c.ctypes.data_as(_dp) for c in cols]
+
+
+def _hits_of(ok, hits):
+    rec = np.zeros(len(ok), dtype=HIT_DTYPE)
+    for k in np.flatnonzero(ok):
+        h = hits[k]
+        rec[k] = (h.t, tuple(h.p), tuple(h.n), h.mat, h.front_face)
+    return ok.astype(bool), rec
+
+
+def ref_scene_intersect(scene: Scene, rays):
+    """The reference's own Scene::intersect of an rt_ray array (oracle/_ref,
+    container only): (hit flags, HIT_DTYPE records; a miss is zeros)."""
+    lib = ref_lib()
+    n, _keep, (o, d, t0, t1) = _ray_args(rays)
+    ok, hits = (C.c_int * n)(), (OracleHit * n)()
+    lib.ref_scene_intersect_batch.argtypes = [C.POINTER(SceneDesc), C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int),
+                                              C.POINTER(OracleHit)]
+    lib.ref_scene_intersect_batch(scene.desc_ptr, n, o, d, t0, t1, ok, hits)
+    return _hits_of(np.array(ok[:], dtype=np.int32), hits)
+
+
+def ref_scene_occluded(scene: Scene, rays) -> np.ndarray:
+    """The reference's own Scene::occluded of an rt_ray array, as bools (container only)."""
+    lib = ref_lib()
+    n, _keep, (o, d, t0, t1) = _ray_args(rays)
+    ok = (C.c_int * n)()
+    lib.ref_scene_occluded_batch.argtypes = [C.POINTER(SceneDesc), C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]
+    lib.ref_scene_occluded_batch(scene.desc_ptr, n, o, d, t0, t1, ok)
+    return np.array(ok[:], dtype=np.int32).astype(bool)
+
+
+def oracle_scene_intersect(scene: Scene, rays):
+    """Scene::intersect of an rt_ray array through the oracle: (hit flags,
+    HIT_DTYPE records; a miss is zeros).  TEST ONLY."""
+    lib = oracle_lib()
+    n, (o, d, t0, t1), _ptrs = _ray_args(rays)
+    ok, hits = np.zeros(n, dtype=np.int32), (OracleHit * n)()
+    for k in range(n):
+        ok[k] = lib.oracle_scene_intersect(scene.desc_ptr, o[k].ctypes.data_as(_dp), d[k].ctypes.data_as(_dp),
+                                           float(t0[k]), float(t1[k]), C.byref(hits[k]))
+    return _hits_of(ok, hits)
+
+
+def _trace_rays(lib, fn, scene: Scene, origins, dirs):
+    o = np.ascontiguousarray(origins, dtype=np.float64)
+    d = np.ascontiguousarray(dirs, dtype=np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and dirs must both be (n, 3) arrays, got {o.shape} and {d.shape}")
+    n = len(o)
+    rgb, ni, no = np.zeros((n, 3)), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    f = getattr(lib, fn)
+    f.argtypes = [C.POINTER(SceneDesc), C.c_int, _dp, _dp, _dp, C.c_void_p, C.c_void_p]
+    f(scene.desc_ptr, n, o.ctypes.data_as(_dp), d.ctypes.data_as(_dp), rgb.ctypes.data_as(_dp),
+      ni.ctypes.data_as(C.c_void_p), no.ctypes.data_as(C.c_void_p))
+    return rgb, ni.astype(np.int64), no.astype(np.int64)
+
+
+def oracle_trace_rays(scene: Scene, origins, dirs):
+    """Tracer::trace(Ray(o, d)) of every ray through the oracle, the ray built
+    once by the Ray constructor: (rgb (n, 3), n_intersect (n,), n_occluded
+    (n,)).  What oracle_trace gives for finite rays (up to its mean of 8 equal
+    samples), and the reference's answer where a component is not finite:
+    oracle_trace's ray passes through the camera and is normalised twice,
+    which turns an infinite direction into (0, 1, 0).  TEST ONLY."""
+    return _trace_rays(oracle_lib(), "oracle_trace_rays", scene, origins, dirs)
+
+
+def ref_trace(scene: Scene, origins, dirs):
+    """The reference's own Tracer::trace(Ray(o, d)) of every ray (oracle/_ref, container only)."""
+    return _trace_rays(ref_lib(), "ref_trace_batch", scene, origins, dirs)
+
+
+def ref_shade(scene: Scene, hits, wo):
+    """The reference's own shade_lambert_phong of every hit (a HIT_DTYPE array)
+    and view direction: (rgb (n, 3), n_occluded (n,)) (oracle/_ref, container only)."""
+    lib = ref_lib()
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    w = np.ascontiguousarray(wo, dtype=np.float64)
+    n = len(hits)
+    rgb, no = np.zeros((n, 3)), np.zeros(n, dtype=np.uint64)
+    lib.ref_shade_batch.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, _dp, _dp, C.c_void_p]
+    lib.ref_shade_batch(scene.desc_ptr, n, hits.ctypes.data_as(C.c_void_p), w.ctypes.data_as(_dp),
+                        rgb.ctypes.data_as(_dp), no.ctypes.data_as(C.c_void_p))
+    return rgb, no.astype(np.int64)
+
+
 def to_rgb8(fb: np.ndarray) -> np.ndarray:
     fb = np.ascontiguousarray(fb, dtype=np.float64)
     out = np.zeros(fb.shape, dtype=np.uint8)

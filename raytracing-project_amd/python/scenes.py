@@ -826,6 +826,322 @@ def graph_scene(seed: int, dpi: int = 16) -> dict:
     return _base(objs, recursion=3, dpi=dpi, lights=lights)
 
 
+# --------------------------------------------------- leaf-parameter scenes
+# Edge values of the leaf primitives' own parameters; the reference's loader
+# checks none of them (json_loader.cpp:211-297).
+LEAF_HALF_NORMALS = ([0, 0, 0], [0, 1e-200, 0], [0, 1e200, 1e200], [0, 5e-324, 0], [0, 6e149, 8e149])
+LEAF_BELT_HALF = (0, -0.1, 1.0, 2.0)
+LEAF_BUTTON_OUTER = (0, -1, math.pi, 4.0)
+LEAF_RING_WIDTH = (0, 1.0)
+LEAF_BUTTON_DIR = ([0, 0, 0], [0, 0, 1e-7], [1e200, 0, 0])
+LEAF_INDEX = (0, -1.5, 1e-300, 1e300)
+LEAF_COEFF = ([-1, -0.5, -0.3], [2, 2, 2], [1, -1, 0])
+LEAF_LAYOUT = {   # case -> layout: few (< 4 bounded objects), wave (>= 4), bvh (> 256 objects)
+    "neg_radius_bare": "few", "neg_radius_bare_bvh": "bvh", "neg_radius_glass": "wave", "neg_radius_csg": "wave",
+    "neg_radius_xform": "few", "radius_edges": "few", "radius_edges_wave": "wave", "radius_edges_bvh": "bvh",
+    "huge_enclosing": "wave", "half_normals_few": "few", "half_normals": "wave", "poke_params_few": "few",
+    "poke_params": "wave", "poke_params_bvh": "bvh", "index_edges": "wave", "index_huge": "wave",
+    "index_medium0": "few", "coeff_edges": "wave", "neg_radius_eager": "wave"}
+# the cases with an eager program (a transform inside a CSG operand): the general kernels
+LEAF_EAGER_CASES = ("neg_radius_eager",)
+# marker colours (diffuse) the CPU tests find a case's objects by
+LEAF_NEG_COL, LEAF_ZERO_COL, LEAF_TINY_COL, LEAF_HUGE_COL = [0.9, 0.3, 0.2], [0.9, 0.1, 0.9], [0.1, 0.9, 0.9], [0.5, 0.6, 0.5]
+LEAF_POKE_DIR = [0.2, 0.1, 1.0]
+
+
+def _poke(c, r, **kw):
+    p = {"position": [float(v) for v in c], "radius": r, "button_dir": list(LEAF_POKE_DIR)}
+    p.update(kw)
+    return {"pokeball": p}
+
+
+def _leaf_extra(layout: str) -> list:
+    """What a layout adds to a case's own objects: nothing (few), four
+    ordinary spheres at the frame's corners (wave: the capsule and cone tests
+    run), or the lattice of shading_layout("bvh") (the wave BVH)."""
+    if layout == "few":
+        return []
+    if layout == "bvh":
+        return shading_layout("bvh")[1:]
+    return [_sph([-1.7, 1.1, -2.0], 0.3, _mat([0.3, 0.8, 0.3])),
+            _sph([1.7, 1.1, -2.0], 0.3, _mat([0.2, 0.5, 0.8], reflected=[0.4, 0.4, 0.4])),
+            _sph([-1.8, -0.8, -0.5], 0.3, _mat([0.8, 0.8, 0.2])),
+            _sph([1.8, -0.8, -0.5], 0.3, _mat([0.7, 0.3, 0.7], refracted=[0.5, 0.5, 0.5]), index=1.5)]
+
+
+def leaf_poke_variants() -> list[dict]:
+    """The odd pokeball parameter sets of poke_params, one key each (the last: custom colours)."""
+    out = [{"belt_half": v} for v in LEAF_BELT_HALF] + [{"button_outer": v} for v in LEAF_BUTTON_OUTER]
+    out += [{"ring_width": v} for v in LEAF_RING_WIDTH]
+    # (a button wide enough to be seen where the fallback direction +Y puts it)
+    out += [{"button_dir": list(v), "button_outer": 0.9, "ring_width": 0.3} for v in LEAF_BUTTON_DIR]
+    grey = _mat([0.4, 0.4, 0.4])
+    out.append({"colors": {"top": _mat([0.9, 0.2, 0.2]), "bottom": _mat([0.9, 0.9, 0.9]), "ring": grey, "button": grey,
+                           "belt": _mat([0.1, 0.1, 0.1], reflected=[0.5, 0.5, 0.5], refracted=[0.3, 0.3, 0.3])}})
+    return out
+
+
+def leaf_cases(dpi: int = 12) -> dict[str, dict]:
+    """Hand-written scenes whose leaves carry parameters no other family has
+    (tests/test_leaf_scenes.py, tests/test_gpu_leaves.py); the odd leaf is what
+    the camera looks at, LEAF_LAYOUT names the layout around it:
+      neg_radius_*   a sphere and a pokeball of negative radius ((p - c) / r
+                     flips front_face, the pokeball's regions and eta): bare,
+                     as glass at recursion 4, as left and right operand of
+                     every operator (binary csg and n-ary), under a Scaling
+                     and a Rotation
+      radius_edges*  radius 0 and 1e-7 over a sphere of radius 1e6 as the floor
+      huge_enclosing a sphere of radius 1e6 around the eye
+      half_normals*  LEAF_HALF_NORMALS (zero and underflowing -> +Y,
+                     overflowing -> n = 0: never hit, all of space as an
+                     interval) bare, under a Translation and as CSG operands
+      poke_params*   leaf_poke_variants()
+      neg_radius_eager  negative-radius leaves as untransformed operands of
+                     eager programs (the other operand under a transform):
+                     sphere_interval / pick_region of the eager interpreter
+      index_edges    index 0 and -1.5 on spheres with kt > 0; index_huge:
+                     1e-300 and 1e300; index_medium0: medium.index 0.  The
+                     last two at recursion 2: eta = 1e-300 or 0 sends the
+                     refracted ray along -n through the centre, and whether
+                     it leaves (eta = 1e300 or 1 / 0 times 1 - cos^2, which is
+                     0 or an ulp) is decided by the origin's last bits - the
+                     oracle alone was unstable on 28 of 33 such rays - so the
+                     ray that enters is traced and its exit is not
+      coeff_edges    reflected / refracted blocks LEAF_COEFF (kr, kt < 0, > 1, 0)"""
+    sc = {}
+
+    def put(name, objs, recursion=3, floor=True, index=1.0):
+        d = _base(([_floor()] if floor else []) + objs + _leaf_extra(LEAF_LAYOUT[name]), recursion=recursion, dpi=dpi)
+        d["medium"]["index"] = index
+        sc[name] = d
+
+    neg = _mat(LEAF_NEG_COL)
+    bare = [_sph([-0.7, 0.1, -1.0], -0.55, neg), _poke([0.7, 0.1, -1.0], -0.55)]
+    put("neg_radius_bare", bare)
+    put("neg_radius_bare_bvh", bare)
+    glass = _mat(LEAF_NEG_COL, reflected=[0.3, 0.3, 0.3], refracted=[0.5, 0.5, 0.5])
+    put("neg_radius_glass", [
+        _sph([-0.7, 0.1, -1.0], -0.55, glass, index=1.5),
+        _poke([0.7, 0.1, -1.0], -0.55, colors={"top": dict(glass), "bottom": dict(glass)}),
+        _sph([0.0, -0.7, -2.5], 0.5, _mat([0.2, 0.3, 0.9]))], recursion=4)
+    objs = []
+    for k, (op, side) in enumerate((o, s) for o in ("union", "intersection", "difference") for s in (0, 1)):
+        for form in (0, 1):
+            c = [-1.25 + 0.5 * k, -0.5 + 1.0 * form, -1.0]
+            odd = _sph(c, -0.3, neg) if (k + form) % 2 else _poke(c, -0.3)
+            other = _sph([c[0] + 0.12, c[1] + 0.1, c[2] + 0.15], 0.25, _mat([0.2, 0.4, 0.9]))
+            third = _sph([c[0] - 0.05, c[1] - 0.12, c[2] + 0.1], 0.28, _mat([0.3, 0.8, 0.3]))
+            if form == 0:
+                a, b = (odd, other) if side == 0 else (other, odd)
+                objs.append({"csg": {"operator": op, "left": a, "right": b}})
+            else:
+                objs.append({op: [odd, other, third] if side == 0 else [other, third, odd]})
+    put("neg_radius_csg", objs)
+    put("neg_radius_xform", [_sc([1.3, 0.7, 1.0], _sph([-0.6, 0.2, -1.0], -0.5, neg)),
+                             _rot(30, 2, _poke([0.6, -0.3, -1.0], -0.5))])
+    edges = [_sph([0, -1e6 - 1.2, 0], 1e6, _mat(LEAF_HUGE_COL)), _sph([0.0, 0.3, -1.0], 0.0, _mat(LEAF_ZERO_COL)),
+             _sph([0.5, 0.2, -1.0], 1e-7, _mat(LEAF_TINY_COL))]
+    put("radius_edges", edges, floor=False)
+    put("radius_edges_wave", edges, floor=False)
+    put("radius_edges_bvh", edges, floor=False)
+    put("huge_enclosing", [_sph([0, 0, 0], 1e6, _mat([0.4, 0.5, 0.8])), _sph([0.0, 0.0, -1.5], 0.6, _mat(LEAF_NEG_COL))])
+    # half-spaces: [0, 0, 0] is the floor, the translated [0, 1e-200, 0] a ceiling at y = 1.5
+    hm = [_mat([0.5, 0.6, 0.5]), _mat([0.6, 0.5, 0.5]), _mat([0.9, 0.0, 0.9]), _mat([0.5, 0.5, 0.6]), _mat([0.6, 0.6, 0.4])]
+    planes = []
+    for k, n in enumerate(LEAF_HALF_NORMALS):
+        y = [-1.2, -1.3, -1.0, -1.4, 0.0][k]
+        planes.append({"halfSpace": {"position": [0, y, -6.0 if k == 4 else 0], "normal": list(n), "color": hm[k]}})
+        up = [3.0, 2.7, 2.0, 3.2, 0.0][k]
+        planes.append(_tr([0, up, -1.0 if k == 4 else 0],
+                          {"halfSpace": {"position": [0, -1.2, -6.0 if k == 4 else 0], "normal": list(n), "color": hm[k]}}))
+    put("half_normals_few", planes, floor=False)
+    cut = []
+    for k, n in enumerate(LEAF_HALF_NORMALS):
+        c = [-1.2 + 0.6 * k, -0.4, -1.0]
+        h = {"halfSpace": {"position": list(c), "normal": list(n), "color": _mat([0.9, 0.9, 0.1 * k])}}
+        cut.append({"difference": [_sph(c, 0.28, _mat([0.2, 0.4, 0.9])), h]})
+        c2 = [c[0], 0.5, -1.0]
+        h2 = {"halfSpace": {"position": list(c2), "normal": list(n), "color": _mat([0.1 * k, 0.9, 0.9])}}
+        cut.append({"csg": {"operator": "intersection", "left": h2, "right": _sph(c2, 0.28, _mat([0.9, 0.4, 0.2]))}})
+    put("half_normals", planes + cut, floor=False)
+    # (the button_dir variants in the bottom row: their +Y button is seen from above)
+    balls = [_poke([-1.4 + 0.7 * (k % 5), 0.7 - 0.65 * (k // 5), -1.0], 0.3, **kw) for k, kw in enumerate(leaf_poke_variants())]
+    put("poke_params_few", [balls[1], balls[7], balls[10]])
+    put("poke_params", balls, recursion=2)
+    put("poke_params_bvh", balls, recursion=2)
+    tm = _mat([0.3, 0.5, 0.8], refracted=[0.6, 0.6, 0.6])
+    put("index_edges", [_sph([-0.6 + 1.2 * k, 0.0, -1.0], 0.5, tm, index=v) for k, v in enumerate(LEAF_INDEX[:2])])
+    put("index_huge", [_sph([-0.6 + 1.2 * k, 0.0, -1.0], 0.5, tm, index=v) for k, v in enumerate(LEAF_INDEX[2:])],
+        recursion=2)
+    put("index_medium0", [_sph([-0.6, 0.0, -1.0], 0.5, tm, index=1.5), _sph([0.6, 0.0, -1.0], 0.5, tm, index=0)],
+        recursion=2, index=0)
+    blue = _mat([0.2, 0.4, 0.9])
+    put("neg_radius_eager", [
+        {"union": [_sph([-1.0, 0.3, -1.0], -0.45, neg), _tr([-1.0, 0.0, 0.0], _sph([0.4, 0.0, -1.0], 0.3, blue))]},
+        {"csg": {"operator": "difference", "left": _poke([0.1, 0.3, -1.0], -0.45),
+                 "right": _rot(20, 1, _sph([0.5, 0.6, -0.7], 0.3, blue))}},
+        {"intersection": [_sc([1.0, 1.2, 1.0], _sph([1.2, 0.25, -1.0], 0.5, blue)),
+                          _sph([1.2, 0.3, -1.0], -0.45, glass, index=1.5)]}], recursion=4)
+    put("coeff_edges", [_sph([-0.8 + 0.8 * k, 0.6, -1.0], 0.36, _mat([0.8, 0.5, 0.2], reflected=list(v)))
+                        for k, v in enumerate(LEAF_COEFF)] +
+                       [_sph([-0.8 + 0.8 * k, -0.4, -1.0], 0.36, _mat([0.2, 0.5, 0.8], refracted=list(v)), index=1.4)
+                        for k, v in enumerate(LEAF_COEFF)])
+    assert set(sc) == set(LEAF_LAYOUT)
+    return sc
+
+
+def leaf_scene(seed: int, dpi: int = 12) -> dict:
+    """graph_scene(seed) with its leaves' parameters replaced, each with
+    probability 1/3, by a draw from the edge lists above: a negated, zero or
+    1e-7 radius, an odd pokeball parameter set, an odd sphere index, odd
+    reflected / refracted blocks, an odd half-space normal."""
+    import random
+    rnd = random.Random(7919 * seed + 13)
+    scene = graph_scene(seed, dpi=dpi)
+    variants = leaf_poke_variants()[:-1]
+
+    def walk(node, top):
+        (kind, body), = node.items()
+        if kind in ("sphere", "pokeball"):
+            if rnd.random() < 1 / 3:
+                body["radius"] = rnd.choice([-body["radius"], -body["radius"], 0.0, 1e-7])
+            if kind == "pokeball" and rnd.random() < 1 / 3:
+                body.update(copy.deepcopy(rnd.choice(variants)))
+            if kind == "sphere":
+                if rnd.random() < 1 / 3:
+                    body["index"] = rnd.choice(LEAF_INDEX)
+                if rnd.random() < 1 / 3:
+                    body["color"][rnd.choice(["reflected", "refracted"])] = list(rnd.choice(LEAF_COEFF))
+        elif kind == "halfSpace":
+            # (the floor keeps its normal: the scene stays a scene over a floor)
+            if not top and rnd.random() < 1 / 3:
+                body["normal"] = list(rnd.choice(LEAF_HALF_NORMALS))
+        elif kind == "csg":
+            walk(body["left"], False)
+            walk(body["right"], False)
+        elif kind in ("union", "intersection", "difference"):
+            for sub in body:
+                walk(sub, False)
+        else:
+            walk(body["subject"], False)
+
+    for obj in scene["objects"]:
+        walk(obj, True)
+    return scene
+
+
+# ------------------------------------------- non-finite and overflowing rays
+ODD_RAY_SCENES = ("config5", "torture/halfspace_in_csg", "bvh/ties", "leaf/radius_edges_wave")
+ODD_RAY_N = 64
+
+
+def odd_ray_scene(name: str) -> str:
+    """JSON text of an ODD_RAY_SCENES entry (the first three as tests/test_gpu_query.py loads them)."""
+    if name == "config5":
+        return config_json(5, dpi=24)[0]
+    if name.startswith("torture/"):
+        return json.dumps(torture_scenes(dpi=24)[name[8:]])
+    if name == "bvh/ties":
+        return json.dumps(bvh_scenes(16)["ties"])
+    return json.dumps(leaf_cases()[name[5:]])
+
+
+def odd_ray_pixels(W: int, H: int) -> list:
+    """The 64 pixels (an 8 x 8 grid) whose pixel-centre camera rays the groups are made from."""
+    return [((2 * (k % 8) + 1) * W // 16, (2 * (k // 8) + 1) * H // 16) for k in range(ODD_RAY_N)]
+
+
+def odd_ray_groups(o, d) -> dict:
+    """Ray groups with non-finite or overflowing components, made from 64
+    ordinary rays (o, d: (64, 3), d of unit length): tag -> (o, d, tmin,
+    tmax).  Which component is odd rotates with the ray's index."""
+    import numpy as np
+    o, d = np.asarray(o, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    n = len(o)
+    assert o.shape == d.shape == (ODD_RAY_N, 3)
+    nan, inf = float("nan"), float("inf")
+    ax = np.arange(n) % 3
+    rows = np.arange(n)
+
+    def one(a, v):
+        a = a.copy()
+        a[rows, ax] = v
+        return a
+
+    def rng(tmin=1e-4, tmax=inf):
+        return np.full(n, tmin), np.full(n, tmax)
+
+    g = {}
+    g["o one nan"] = (one(o, nan), d, *rng())
+    g["o all nan"] = (np.full((n, 3), nan), d, *rng())
+    g["o +inf"] = (one(o, inf), d, *rng())
+    g["o -inf"] = (one(o, -inf), d, *rng())
+    g["d one nan"] = (o, one(d, nan), *rng())
+    g["d all nan"] = (o, np.full((n, 3), nan), *rng())
+    g["d inf"] = (o, one(d, np.where(rows % 2 == 0, inf, -inf)), *rng())
+    g["d 1e200"] = (o, d * 1e200, *rng())
+    g["d 1e-200"] = (o, d * 1e-200, *rng())
+    g["d subnormal"] = (o, d * 1e-310, *rng())
+    # the `L > 1e-6` edge of Dir3::normalized from both sides: exactly 1e-6 long
+    # (-> (0, 1, 0)), one ulp longer, and the ray's own direction 1e-6 (1 -+ 1e-9) long
+    edge = d * 1e-6
+    k = rows % 4
+    edge[k == 0] = [0.0, 0.0, -1e-6]
+    edge[k == 1] = [0.0, 0.0, -float(np.nextafter(1e-6, 1.0))]
+    edge[k == 2] *= 1.0 - 1e-9
+    edge[k == 3] *= 1.0 + 1e-9
+    g["d 1e-6 long"] = (o, edge, *rng())
+    g["tmin nan"] = (o, d, *rng(tmin=nan))
+    g["tmin -inf"] = (o, d, *rng(tmin=-inf))
+    g["tmin +inf"] = (o, d, *rng(tmin=inf))
+    g["tmax nan"] = (o, d, *rng(tmax=nan))
+    g["tmax -inf"] = (o, d, *rng(tmax=-inf))
+    g["both nan"] = (o, d, *rng(nan, nan))
+    return g
+
+
+def odd_hit_groups(H, wo) -> dict:
+    """Shading inputs with a NaN or an infinity in t, p, n or wo, made from
+    ordinary hits H (an rt_hit record array) and view directions wo: tag ->
+    (hits, wo).  Which component is odd rotates with the index."""
+    import numpy as np
+    H, wo = np.asarray(H).copy(), np.asarray(wo, dtype=np.float64).copy()
+    ax, rows = np.arange(len(H)) % 3, np.arange(len(H))
+    out = {}
+    for f in ("t", "p", "n", "wo"):
+        for tag, v in (("nan", float("nan")), ("+inf", float("inf")), ("-inf", -float("inf"))):
+            h, w = H.copy(), wo.copy()
+            if f == "t":
+                h["t"] = v
+            elif f == "wo":
+                w[rows, ax] = v
+            else:
+                h[f][rows, ax] = v
+            out[f"{f} {tag}"] = (h, w)
+    h = H.copy()
+    h["t"], h["p"], h["n"] = float("nan"), float("nan"), float("nan")
+    out["all nan"] = (h, np.full_like(wo, float("nan")))
+    # a finite wo whose specular power overflows (unit wo: r.wo <= 1)
+    out["wo 1e200"] = (H.copy(), wo * 1e200)
+    # and one whose power stays finite above 1 (r.wo up to 10: 1e5 at shininess 5, 1e64 at 64)
+    out["wo x10"] = (H.copy(), wo * 10.0)
+    return out
+
+
+def zero_radius_centre_rays(centre) -> tuple:
+    """64 axis-parallel rays aimed exactly through `centre` (the zero_radius
+    sphere's): oc is a multiple of d, so disc == 0 exactly, the hit point is
+    the centre and outward = 0 / 0.  (o, d, tmin, tmax)."""
+    import numpy as np
+    o, d = np.zeros((ODD_RAY_N, 3)), np.zeros((ODD_RAY_N, 3))
+    for k in range(ODD_RAY_N):
+        a, sgn = k % 3, 1.0 if (k // 3) % 2 == 0 else -1.0
+        d[k, a] = sgn
+        o[k] = centre
+        o[k, a] -= sgn * (0.25 + 0.125 * (k // 6))
+    return o, d, np.full(ODD_RAY_N, 1e-4), np.full(ODD_RAY_N, float("inf"))
+
+
 # ------------------------------------------------------------ shading scenes
 SHADING_LAYOUTS = ("few", "wave", "csg", "xform", "bvh")
 SHADING_EXPONENTS = (0, 1, 2, 3, 5, 7, 127, 255, 1000, 1023, 1024, 2000, 12.5, 0.5, -2)

@@ -32,8 +32,13 @@ turned into IR by our loader (librt_host.so).  Outputs are data only:
                scenes.graph_scene at GRAPH_SEEDS), both modes, at GRAPH_DPI,
                and intersect / interval answers of every top-level object of
                the named cases for 64 rays per case
+  leaves.npz, leaf_seeds.npz, leaf_rays.npz
+               frames + counts of the leaf-parameter scenes (scenes.leaf_cases,
+               scenes.leaf_scene at LEAF_SEEDS), both modes, at LEAF_DPI, and
+               Scene::intersect / Scene::occluded of the non-finite and
+               overflowing ray groups (scenes.odd_ray_groups)
 
-Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh shading graph]
+Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh shading graph leaves]
 """
 from __future__ import annotations
 
@@ -333,6 +338,72 @@ def make_graph():
     print("graph:", len(data))
 
 
+LEAF_SEEDS = (1, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13)
+LEAF_DPI = 12   # 48 x 36 frames
+
+
+def _ref_frames(data, name, d):
+    sc = rtamd.load_scene_from_json_text(json.dumps(d))
+    for mode in (0, 1):
+        with quiet_stdout():
+            fb, ni, no = rtamd.ref_render(sc, sc.width, sc.height, mode)
+        data[f"{name}/{mode}/fb"] = fb
+        data[f"{name}/{mode}/counts"] = np.array([ni, no], dtype=np.int64)
+
+
+def make_leaves():
+    """The leaf-parameter scenes (scenes.leaf_cases -> leaves.npz,
+    scenes.leaf_scene at LEAF_SEEDS -> leaf_seeds.npz), both modes, and the
+    reference's Scene::intersect / Scene::occluded of the non-finite and
+    overflowing ray groups (scenes.odd_ray_groups on scenes.ODD_RAY_SCENES ->
+    leaf_rays.npz: per "<scene>|<group>" the rays (o, d, tmin, tmax), the hit
+    flags, the hit records (a miss is zeros) and the occluded flags)."""
+    lib = rtamd.ref_lib()
+    data = {"dpi": np.array(LEAF_DPI, dtype=np.int64)}
+    for name, d in scenes.leaf_cases(dpi=LEAF_DPI).items():
+        _ref_frames(data, name, d)
+    np.savez_compressed(os.path.join(HERE, "leaves.npz"), **data)
+    print("leaves:", len(data))
+    data = {"dpi": np.array(LEAF_DPI, dtype=np.int64), "seeds": np.array(LEAF_SEEDS, dtype=np.int64)}
+    for seed in LEAF_SEEDS:
+        _ref_frames(data, f"seed{seed}", scenes.leaf_scene(seed, dpi=LEAF_DPI))
+    np.savez_compressed(os.path.join(HERE, "leaf_seeds.npz"), **data)
+    print("leaf_seeds:", len(data))
+    data = {}
+    for name in scenes.ODD_RAY_SCENES:
+        sc = rtamd.load_scene_from_json_text(scenes.odd_ray_scene(name))
+        o, d = np.zeros((scenes.ODD_RAY_N, 3)), np.zeros((scenes.ODD_RAY_N, 3))
+        for k, (i, j) in enumerate(scenes.odd_ray_pixels(sc.width, sc.height)):
+            lib.ref_camera_ray(sc.desc_ptr, i, j, 0.0, 0.0, 0, o[k].ctypes.data_as(_dp), d[k].ctypes.data_as(_dp))
+        groups = dict(scenes.odd_ray_groups(o, d))
+        if name.startswith("leaf/"):
+            zero = [b["sphere"]["position"] for b in scenes.leaf_cases()[name[5:]]["objects"]
+                    if "sphere" in b and b["sphere"]["radius"] == 0.0][0]
+            groups["zero radius centre"] = scenes.zero_radius_centre_rays(zero)
+        for tag, g in groups.items():
+            rays = rtamd.make_rays(*g)
+            ok, rec = rtamd.ref_scene_intersect(sc, rays)
+            key = f"{name}|{tag}"
+            data[key + "/rays"] = np.concatenate([rays["o"], rays["d"], rays["tmin"][:, None], rays["tmax"][:, None]], axis=1)
+            data[key + "/ok"] = ok.astype(np.int8)
+            data[key + "/hit"] = np.concatenate([rec["t"][:, None], rec["p"], rec["n"], rec["mat"][:, None].astype(float),
+                                                 rec["front_face"][:, None].astype(float)], axis=1)
+            data[key + "/occ"] = rtamd.ref_scene_occluded(sc, rays).astype(np.int8)
+            # Tracer::trace of the same rays (its range is its own: tmin / tmax play no part)
+            rgb, ni, no = rtamd.ref_trace(sc, rays["o"], rays["d"])
+            data[key + "/rgb"] = rgb
+            data[key + "/counts"] = np.stack([ni, no], axis=1)
+        # shade_lambert_phong of the base rays' hits with odd fields (scenes.odd_hit_groups)
+        base = rtamd.make_rays(o, d)
+        ok, rec = rtamd.ref_scene_intersect(sc, base)
+        for tag, (H, wo) in scenes.odd_hit_groups(rec[ok], -d[ok]).items():
+            rgb, no = rtamd.ref_shade(sc, H, wo)
+            data[f"{name}|shade {tag}/rgb"] = rgb
+            data[f"{name}|shade {tag}/no"] = no
+    np.savez_compressed(os.path.join(HERE, "leaf_rays.npz"), **data)
+    print("leaf_rays:", len(data))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         for what in sys.argv[1:]:
@@ -348,3 +419,4 @@ if __name__ == "__main__":
     make_bvh()
     make_shading()
     make_graph()
+    make_leaves()

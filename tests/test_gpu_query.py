@@ -174,6 +174,49 @@ def check_hits(c, rays, got, ref_hit, ref_rec, what, step=1e-7, scale=None):
     return mx
 
 
+def same_value(got, ref, tol=TOL, relative=True):
+    """Elementwise: NaN where ref is NaN, the same infinity where ref is
+    infinite, within tol (relative to max(1, |ref|), or absolute) where ref is
+    finite."""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        fin = np.isfinite(ref)
+        close = np.abs(got - ref) <= tol * (np.maximum(1.0, np.abs(ref)) if relative else 1.0)
+        return np.where(fin, close & np.isfinite(got), (got == ref) | (np.isnan(got) & np.isnan(ref)))
+
+
+def check_hits_every_ray(rays, got, ref_hit, ref_rec, what):
+    """check_hits for rays whose oracle answer may be non-finite (a NaN or
+    infinite ray component, tests/test_gpu_leaves.py): the same bar where the
+    oracle is finite, NaN for NaN and the same infinity otherwise, and no ray
+    left out - the reference's answer on such a ray is exact, not unstable.
+    Returns the largest finite (t, p, n) differences."""
+    assert len(got) == len(rays) == len(ref_hit)
+    g = got.records
+    bad = (got.hit != ref_hit)
+    both = got.hit & ref_hit
+    bad |= both & ((g["mat"] != ref_rec["mat"]) | (g["front_face"] != ref_rec["front_face"]))
+    bad |= both & ~(same_value(g["t"], ref_rec["t"]) & same_value(g["p"], ref_rec["p"]).all(axis=1)
+                    & same_value(g["n"], ref_rec["n"], relative=False).all(axis=1))
+    miss = g[~got.hit]
+    assert np.all(miss["mat"] == -1) and not miss["t"].any() and not miss["p"].any() and not miss["n"].any() \
+        and not miss["front_face"].any(), what
+
+    def largest(f, rel):
+        a, b = g[f][both].reshape(-1), ref_rec[f][both].reshape(-1)
+        k = np.isfinite(b) & np.isfinite(a)
+        return float((np.abs(a[k] - b[k]) / (np.maximum(1.0, np.abs(b[k])) if rel else 1.0)).max(initial=0.0))
+
+    mx = (largest("t", True), largest("p", True), largest("n", False))
+    nonfinite = int((both & ~(np.isfinite(ref_rec["t"]) & np.isfinite(ref_rec["p"]).all(axis=1)
+                              & np.isfinite(ref_rec["n"]).all(axis=1))).sum())
+    print(f"  {what}: {len(rays)} rays, {int(ref_hit.sum())} hits ({nonfinite} non-finite), max rel dt={mx[0]:.3g} "
+          f"dp={mx[1]:.3g} abs dn={mx[2]:.3g}, left out 0")
+    wrong = np.flatnonzero(bad).tolist()
+    assert not wrong, (what, wrong[:8], [(g[k], ref_rec[k], bool(ref_hit[k])) for k in wrong[:2]])
+    return mx
+
+
 def check_occluded(c, rays, got, ref, what, step=1e-7):
     assert got.dtype == bool and len(got) == len(rays)
     bad = np.flatnonzero(got != ref)
