@@ -443,6 +443,77 @@ struct DevScene {
 __device__ __forceinline__ V3 ld3(const real* p) { return v3(p[0], p[1], p[2]); }
 __device__ __forceinline__ V3 background(const DevScene& S) { return ld3(S.mats[S.bg_mat].albedo); }
 
+// ------------------------------------------- kernel arguments, read again
+// A by-value kernel argument is loaded from the kernarg segment at the
+// kernel's entry, and every field the kernel uses anywhere then sits in an
+// SGPR from there on.  The lean standard kernel needs more SGPRs than it has,
+// and what does not fit travels through lanes of a VGPR (v_writelane /
+// v_readlane: VALU issue slots that compute nothing; tools/isa_spill.py).
+// KA = true (a kernel that hands its arguments down unchanged and asks for
+// it): code reads the fields it needs from the kernarg segment again where it
+// uses them - scalar loads, no VALU slot - so that no field has to stay live
+// from one use to the next.  KA = false: the argument itself, as before.
+//
+// args_again<T>(offset, at): the argument of type T at that offset of the
+// kernarg segment as a local copy (the compiler keeps the fields that are
+// used).  The segment pointer passes through an empty asm that also takes
+// `at`, a wave-uniform value of the loop the caller is in: without it the
+// compiler would hoist the loads out of that loop again.  (Not volatile: a
+// volatile asm counts as a write to memory, after which reads of the scene
+// tables are no longer scalar loads.)
+#define RT_AS_GLOBAL __attribute__((address_space(1)))
+#define RT_AS_CONST __attribute__((address_space(4)))
+template <class T>
+__device__ __forceinline__ T args_again(size_t offset, int at) {
+    static_assert(sizeof(T) % sizeof(uint64_t) == 0 && alignof(T) == alignof(uint64_t), "copied by words");
+    const RT_AS_CONST char* p = (const RT_AS_CONST char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm("" : "+s"(p) : "s"(at));
+    const RT_AS_CONST uint64_t* src = reinterpret_cast<const RT_AS_CONST uint64_t*>(p + offset);
+    T L;
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&L);
+#pragma unroll
+    for (size_t i = 0; i < sizeof(T) / sizeof(uint64_t); ++i) dst[i] = src[i];
+    return L;
+}
+// A pointer read that way says nothing about what it points to; a kernel
+// argument's pointer is known to be global memory, which is what makes a
+// wave-uniform read through it a scalar load.  Passing through the global
+// address space restores that (the asm keeps the two casts from cancelling).
+template <class T>
+__device__ __forceinline__ T* global_table(T* p) {
+    RT_AS_GLOBAL T* g = (RT_AS_GLOBAL T*)p;
+    asm("" : "+s"(g));
+    return (T*)g;
+}
+// The kernel's DevScene (its first argument) again
+template <bool KA>
+__device__ __forceinline__ decltype(auto) scene_again(const DevScene& S, int at) {
+    if constexpr (KA) {
+        DevScene L = args_again<DevScene>(0, at);
+        L.nodes = global_table(L.nodes), L.mats = global_table(L.mats), L.lights = global_table(L.lights);
+        L.dlights = global_table(L.dlights), L.objs = global_table(L.objs), L.ops = global_table(L.ops);
+        L.gb = global_table(L.gb), L.ctab = global_table(L.ctab), L.lrec = global_table(L.lrec);
+        L.lgb = global_table(L.lgb), L.fold = global_table(L.fold), L.worig = global_table(L.worig);
+        L.wchunk = global_table(L.wchunk);
+        return L;
+    } else {
+        return (S);
+    }
+}
+
+// Wave-uniform flags kept as one scalar integer instead of a 64-bit lane mask
+// (one SGPR, tested by a scalar compare), built from lane masks by scalar
+// integer operations alone: mask_lacks(m) is 0 exactly when m has all 64 bits
+// set, mask_bits(m) 0 exactly when m is empty, and a flag is the OR of the
+// conditions that switch it off (0 = on), made opaque so that the compiler
+// does not turn it back into a mask.
+__device__ __forceinline__ uint32_t mask_lacks(uint64_t m) { return ~((uint32_t)m & (uint32_t)(m >> 32)); }
+__device__ __forceinline__ uint32_t mask_bits(uint64_t m) { return (uint32_t)m | (uint32_t)(m >> 32); }
+__device__ __forceinline__ uint32_t scalar_flag(uint32_t off) {
+    asm("" : "+s"(off));
+    return off;
+}
+
 // --------------------------------------------------------------- primitives
 // Sphere::intersect (geometry.cpp:12-37)
 template <class CT>
@@ -1205,18 +1276,21 @@ __device__ __forceinline__ float dot_pk(f2v axy, float az, f2v bxy, float bz) {
     return __builtin_fmaf(az, bz, p.x + p.y);
 }
 
-__device__ __forceinline__ bool ball_touch(const float* g, const FRay& r, float t0, float t1) {
+__device__ __forceinline__ bool ball_touch(float gx, float gy, float gz, float gr, const FRay& r, float t0, float t1) {
     const f2v dxy = f2(r.dx, r.dy);
-    const f2v oxy = f2(r.ox, r.oy) - f2(g[0], g[1]);
-    const float oz = r.oz - g[2];
+    const f2v oxy = f2(r.ox, r.oy) - f2(gx, gy);
+    const float oz = r.oz - gz;
     const float b = dot_pk(oxy, oz, dxy, r.dz);
     const float t = __builtin_fminf(__builtin_fmaxf(-b, t0), t1);   // closest point of the segment
     const f2v qxy = pk_fma(f2s(t), dxy, oxy);
     const float qz = __builtin_fmaf(t, r.dz, oz);
     const float q2 = dot_pk(qxy, qz, qxy, qz);
-    const float e = 4e-6f * (__builtin_fabsf(oxy.x) + __builtin_fabsf(oxy.y) + __builtin_fabsf(oz) + __builtin_fabsf(t) + g[3]);
-    const float R = g[3] + e;
+    const float e = 4e-6f * (__builtin_fabsf(oxy.x) + __builtin_fabsf(oxy.y) + __builtin_fabsf(oz) + __builtin_fabsf(t) + gr);
+    const float R = gr + e;
     return !(q2 > R * R);
+}
+__device__ __forceinline__ bool ball_touch(const float* g, const FRay& r, float t0, float t1) {
+    return ball_touch(g[0], g[1], g[2], g[3], r, t0, t1);
 }
 
 // Compact CSG program [pc0, pc1) on the frame ray r: the root interval.
@@ -1813,7 +1887,7 @@ __device__ __forceinline__ bool record_touch(const float4 c0, const float4 c1, c
 // transposed test per 64 chunks skips every chunk no querying segment can
 // reach, then each surviving chunk runs the object test below.  Occlusion is
 // an OR over objects, so the order is free.
-template <bool EAGER, bool DEEP, bool UO, bool BV = false, bool LEAD = false, class CT>
+template <bool EAGER, bool DEEP, bool UO, bool BV = false, bool LEAD = false, bool KA = false, class CT>
 __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real tmin, real tmax, bool need, bool wave_ok,
                                     CT& cnt, bool regular = true) {
 #if defined(RT_ABL) && RT_ABL == 1   // diagnostic ablation builds only (wrong images): no shadow queries
@@ -1838,7 +1912,9 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
     // without the capsule (a partially active wave, unbounded / non-finite
     // segments, or a lane whose direction is not unit) every object is a
     // candidate and each bounded one gets the per-lane segment test
-    const bool cap = wave_ok && exec_full() && !__any(need && !fin);
+    bool cap;
+    if constexpr (KA) cap = wave_ok && scalar_flag(mask_lacks(__builtin_amdgcn_read_exec()) | mask_bits(__ballot(need && !fin))) == 0;
+    else cap = wave_ok && exec_full() && !__any(need && !fin);
     const float ax = rdlane_f(Ax, f), ay = rdlane_f(Ay, f), az = rdlane_f(Az, f);
     const float bx = rdlane_f(Bx, f), by = rdlane_f(By, f), bz = rdlane_f(Bz, f);
     const float da = (Ax - ax) * (Ax - ax) + (Ay - ay) * (Ay - ay) + (Az - az) * (Az - az);
@@ -1867,7 +1943,7 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
     // half-space by every querying lane's segment against its plane - then
     // the transposed tests over the objects behind them
     const int lead = (BV || !LEAD) ? 0 : S.n_lead;
-    const int nch = BV ? S.n_chunks : (S.n_objs - lead + 63) >> 6;
+    const int nch = BV ? S.n_chunks : (scene_again<KA>(S, f).n_objs - lead + 63) >> 6;
     uint64_t cm = 0;   // (BV) chunks ch & ~63 .. +63 some querying segment can reach
     for (int ch = lead > 0 ? -1 : 0; ch < nch; ++ch) {
         int base;
@@ -1901,13 +1977,15 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
             }
         }
         base = lead + (ch << 6);
-        const int nc = S.n_objs - base;
+        const int n_objs = scene_again<KA>(S, ch).n_objs;
+        const int nc = n_objs - base;
         const int j = base + lane;
         // the object's cull record (CompiledScene::ctab): one 32-byte load on
         // every lane (lanes past the last object re-read it and are masked)
-        const int jr = j < S.n_objs ? j : S.n_objs - 1;
-        const float4 c0 = S.ctab[2 * jr], c1 = S.ctab[2 * jr + 1];
-        const bool pass = (j < S.n_objs) &
+        const int jr = j < n_objs ? j : n_objs - 1;
+        const float4* ctab = scene_again<KA>(S, ch).ctab;
+        const float4 c0 = ctab[2 * jr], c1 = ctab[2 * jr + 1];
+        const bool pass = (j < n_objs) &
                           (cap ? record_touch(c0, c1, K)
                                : __float_as_int(c1.x) != 0);
         // (lane j tests object j only with the whole wave active; otherwise
@@ -1920,8 +1998,8 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
         if constexpr (kCounting<CT>) {
             if (need) {
                 int skipped = 0;
-                for (int o = base; o < S.n_objs && o < base + 64; ++o) {
-                    const int k = S.objs[o].kind;
+                for (int o = base; o < n_objs && o < base + 64; ++o) {
+                    const int k = scene_again<KA>(S, o).objs[o].kind;
                     if (k != rtamd::OBJ_GROUP && k != rtamd::OBJ_NEVER && !((m >> (o - base)) & 1)) ++skipped;
                 }
                 cnt_add(cnt, RT_OPC_CULLED, skipped);
@@ -1931,7 +2009,7 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
         while (m) {
             const int o = base + __builtin_ctzll(m);
             m &= m - 1;
-            const DevObj ob = S.objs[o];
+            const DevObj ob = scene_again<KA>(S, o).objs[o];
             if (ob.kind == rtamd::OBJ_GROUP || ob.kind == rtamd::OBJ_NEVER) continue;
             cnt.ev(EV_SH_CAND);
             cnt.pb(PH_OBJ_PREF);
@@ -1940,7 +2018,7 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
             uint64_t lmask = ~0ull;
             bool use_mask = false;
             if (kCsg<CT> && cap && ob.npb > 0 && exec_full()) {
-                const float* g = S.gb + 4 * (ob.pb0 + (lane < ob.npb ? lane : 0));
+                const float* g = scene_again<KA>(S, o).gb + 4 * (ob.pb0 + (lane < ob.npb ? lane : 0));
                 const bool in = lane < ob.npb;
                 const uint64_t cb = __ballot(in && capsule_touch(g, K));   // leaves the capsule reaches
                 bool seg = cb != 0;
@@ -1958,7 +2036,7 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
                 if (seg) {
                     seg = false;
                     for (uint64_t mm = cb; mm && !seg; mm &= mm - 1) {
-                        const float* gk = S.gb + 4 * (ob.pb0 + __builtin_ctzll(mm));
+                        const float* gk = scene_again<KA>(S, o).gb + 4 * (ob.pb0 + __builtin_ctzll(mm));
                         seg = __any(need && !hit && ball_touch(gk, fr, ftmin, ftmax));
                     }
                 }
@@ -1997,7 +2075,7 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
                     lmask = full ? b : ~0ull;
                 }
             }
-            if (S.cull && ob.has_bound) {   // per-lane segment test (f32, cheaper than an FP64 miss)
+            if (scene_again<KA>(S, o).cull && ob.has_bound) {   // per-lane segment test (f32, cheaper than an FP64 miss)
                 if (!__any(need && !hit && (!regular || ball_touch(ob.fb, fr, ftmin, ftmax)))) {
                     if (need) cnt.inc(RT_OPC_CULLED);
                     cnt.pe(PH_OBJ_PREF);
@@ -2526,7 +2604,7 @@ __device__ __forceinline__ bool cone_touch(const float* g, const Cone& K) {
 #ifndef RT_CAM_RHO0
 #define RT_CAM_RHO0 1
 #endif
-template <bool EAGER, bool DEEP, bool BV = false, bool LEAD = false, bool CAM = false, class CT>
+template <bool EAGER, bool DEEP, bool BV = false, bool LEAD = false, bool CAM = false, bool KA = false, class CT>
 __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin, real tmax, real& t_best,
                                      DHit& best, bool wave_ok, CT& cnt, bool valid = true) {
     cnt.pb(PH_WAVE_SETUP);
@@ -2540,7 +2618,7 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
     const bool fin = __builtin_isfinite(fr.ox + fr.oy + fr.oz + fr.dx + fr.dy + fr.dz);
     // no cone for a partially active wave or non-finite rays: every object is
     // a candidate (the per-lane ball test still runs)
-    const bool cone = S.cull && wave_ok && exec_full() && !__any(valid && !fin) && tmin >= RV(0.0);
+    const bool cone = scene_again<KA>(S, f).cull && wave_ok && exec_full() && !__any(valid && !fin) && tmin >= RV(0.0);
     const float ox = rdlane_f(fr.ox, f), oy = rdlane_f(fr.oy, f), oz = rdlane_f(fr.oz, f);
     const float ax = rdlane_f(fr.dx, f), ay = rdlane_f(fr.dy, f), az = rdlane_f(fr.dz, f);
     // 1 - cos(angle to the axis), >= 0 up to rounding
@@ -2571,7 +2649,7 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
     // bounded one) first, in order, as pseudo-chunk -1; then the transposed
     // tests over the objects behind them (the reference's order throughout)
     const int lead = (BV || !LEAD) ? 0 : S.n_lead;
-    const int nch = BV ? S.n_chunks : (S.n_objs - lead + 63) >> 6;
+    const int nch = BV ? S.n_chunks : (scene_again<KA>(S, f).n_objs - lead + 63) >> 6;
     uint64_t cm = 0;   // (BV) chunks ch & ~63 .. +63 the bundle can reach
     for (int ch = lead > 0 ? -1 : 0; ch < nch; ++ch) {
         int base;
@@ -2601,18 +2679,20 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
         }
         base = lead + (ch << 6);
         const int j = base + lane;
-        const int jr = j < S.n_objs ? j : S.n_objs - 1;   // (see scene_occluded_wave)
-        const float4 c0 = S.ctab[2 * jr], c1 = S.ctab[2 * jr + 1];
+        const int n_objs = scene_again<KA>(S, ch).n_objs;
+        const int jr = j < n_objs ? j : n_objs - 1;   // (see scene_occluded_wave)
+        const float4* ctab = scene_again<KA>(S, ch).ctab;
+        const float4 c0 = ctab[2 * jr], c1 = ctab[2 * jr + 1];
         const int type = __float_as_int(c1.x);
-        const bool pass = (j < S.n_objs) & (type != 0) &
+        const bool pass = (j < n_objs) & (type != 0) &
                           ((type != 2) | wide | cone_touch(c0, c1.y, K));
-        const int nc = S.n_objs - base;
+        const int nc = n_objs - base;
         m = (cone && exec_full()) ? __ballot(pass) : (nc >= 64 ? ~0ull : ((1ull << nc) - 1));
         cnt.pe(PH_WAVE_SETUP);
         if constexpr (kCounting<CT>) {
             int skipped = 0;
-            for (int o = base; o < S.n_objs && o < base + 64; ++o) {
-                const int k = S.objs[o].kind;
+            for (int o = base; o < n_objs && o < base + 64; ++o) {
+                const int k = scene_again<KA>(S, o).objs[o].kind;
                 if (k != rtamd::OBJ_GROUP && k != rtamd::OBJ_NEVER && !((m >> (o - base)) & 1)) ++skipped;
             }
             if (valid) cnt_add(cnt, RT_OPC_CULLED, skipped);
@@ -2621,7 +2701,7 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
         while (m) {
             const int o = base + __builtin_ctzll(m);
             m &= m - 1;
-            const DevObj ob = S.objs[o];
+            const DevObj ob = scene_again<KA>(S, o).objs[o];
             if (ob.kind == rtamd::OBJ_GROUP || ob.kind == rtamd::OBJ_NEVER) continue;
             cnt.ev(EV_PR_CAND);
             cnt.pb(PH_OBJ_PREF);
@@ -2639,7 +2719,7 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
             const bool use_mask = kCsg<CT> && !wide && ob.npb > 0 && exec_full();
 #endif
             if (use_mask) {
-                const float* g = S.gb + 4 * (ob.pb0 + (lane < ob.npb ? lane : 0));
+                const float* g = scene_again<KA>(S, o).gb + 4 * (ob.pb0 + (lane < ob.npb ? lane : 0));
                 const bool in = lane < ob.npb;
                 if (!__any(in && cone_touch(g, K))) {
                     if (valid) cnt.inc(RT_OPC_CULLED);
@@ -2650,7 +2730,7 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
                 const uint64_t b = __ballot(in && line_touch(g, K));
                 lmask = full ? b : ~0ull;
             }
-            if (S.cull && ob.has_bound && !__any(valid && ball_touch(ob.fb, fr, ftmin, (float)closest))) {
+            if (scene_again<KA>(S, o).cull && ob.has_bound && !__any(valid && ball_touch(ob.fb, fr, ftmin, (float)closest))) {
                 if (valid) cnt.inc(RT_OPC_CULLED);
                 cnt.pe(PH_OBJ_PREF);
                 continue;
@@ -2795,7 +2875,7 @@ __device__ __forceinline__ V3 combine(V3 a, V3 b) {   // shading.cpp:6-12
 // LEAD: the wave queries handle CompiledScene::n_lead (the paper and
 // recursion kernels; in the lean standard kernel the extra path cost
 // registers: config 4 kernel 7.2 -> 7.6 ms, profiles/r06_ab/ab_lead.txt)
-template <bool EAGER, bool DEEP, bool DL, int WV, bool UO = RT_STD_UO, bool LEAD = false, class CT>
+template <bool EAGER, bool DEEP, bool DL, int WV, bool UO = RT_STD_UO, bool LEAD = false, bool KA = false, class CT>
 __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t& n_occl, CT& cnt,
                     bool valid = true) {
     // valid = false: a lane of the wave that has nothing to shade (a primary
@@ -2806,7 +2886,9 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
     if (valid) cnt.inc(RT_OPC_SHADE_CALL);
     // WV (wave-level culling; the host picks it for scenes with >= 4 bounded
     // objects, culling on): the capsule test needs every lane active
-    const bool wave_full = WV && __builtin_amdgcn_read_exec() == ~0ull;
+    bool wave_full;
+    if constexpr (KA) wave_full = WV && scalar_flag(mask_lacks(__builtin_amdgcn_read_exec())) == 0;
+    else wave_full = WV && __builtin_amdgcn_read_exec() == ~0ull;
     const V3 n = hit.n;
     const real eps = cmax(RV(1e-3), RV(1e-4) * ht);   // (no zeros)
     // the wave's hit points once per call: the light-centred shadow culls
@@ -2853,12 +2935,13 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
     }
     if (WV) cnt.pb(PH_SHADE2);   // (pass 2 is timed from the end of pass 1; this start is overwritten)
     double* const lc = wave_pool((int)(threadIdx.x >> 6)) + (threadIdx.x & 63);
-    for (int l0 = 0; __any(valid) && l0 < S.n_lights; l0 += 32) {
-        const int l1 = S.n_lights - l0 < 32 ? S.n_lights : l0 + 32;
+    for (int l0 = 0; __any(valid) && l0 < scene_again<KA>(S, l0).n_lights; l0 += 32) {
+        const int n_lights = scene_again<KA>(S, l0).n_lights;
+        const int l1 = n_lights - l0 < 32 ? n_lights : l0 + 32;
         uint32_t lit = 0;
         if (WV) cnt.pb(PH_SHADE1);
         for (int li = l0; li < l1; ++li) {
-            const LightT* L = &S.lights[li];
+            const LightT* L = &scene_again<KA>(S, li).lights[li];
             if (valid) cnt.inc(RT_OPC_LIGHT_EVAL);
             V3 tl = v3(L->pos[0] - hit.p.x, L->pos[1] - hit.p.y, L->pos[2] - hit.p.z);
             real d2 = dot3(tl, tl);
@@ -2898,7 +2981,7 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
                 cnt.pe(PH_SHADOW);
             } else if constexpr (WV) {
                 cnt.pb(PH_SHADOW);
-                occ = scene_occluded_capsule<EAGER, DEEP, UO, false, LEAD>(S, DRay{so, wi}, eps, max_t, need, wave_full, cnt,
+                occ = scene_occluded_capsule<EAGER, DEEP, UO, false, LEAD, KA>(S, DRay{so, wi}, eps, max_t, need, wave_full, cnt,
                                                                            !clamped);
                 cnt.pe(PH_SHADOW);
             } else if (need) {
@@ -2918,13 +3001,13 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
         if (lit != 12345u) continue;
 #endif
         if (!lit) continue;
-        const MatT* m = &S.mats[hit.mat];
+        const MatT* m = &scene_again<KA>(S, l0).mats[hit.mat];
         const real kd = m->kd, ks = m->ks, shin = m->shininess;
         const V3 alb = ld3(m->albedo);
         for (int li = l0; li < l1; ++li) {
             if (!((lit >> (li - l0)) & 1u)) continue;
             cnt.ev(EV_LIGHT2);
-            const LightT* L = &S.lights[li];
+            const LightT* L = &scene_again<KA>(S, li).lights[li];
             V3 wi;
             real dist;
             if (li - l0 < kLightCache) {   // pass 1's values (same lane)
@@ -3174,7 +3257,7 @@ __device__ __forceinline__ V3 trace_wave(const DevScene& S, DRay r0, uint32_t& n
 }
 
 // Tracer::trace_recursive (tracer.cpp:22-73) as an explicit frame stack.
-template <bool EAGER, bool DEEP, bool SECONDARY, bool DL, int WV, class CT>
+template <bool EAGER, bool DEEP, bool SECONDARY, bool DL, int WV, bool KA = false, class CT>
 __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect, uint32_t& n_occl, CT& cnt) {
 #ifndef RT_OLD_TRACE
     if constexpr (SECONDARY && WV) return trace_wave<EAGER, DEEP, DL, WV>(S, r, n_isect, n_occl, cnt);
@@ -3191,14 +3274,14 @@ __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect
             // miss lanes stay in shade() (valid = false) so that the wave
             // stays fully active for the wave-level shadow queries
             cnt.pb(PH_PRIMARY);
-            const bool hit = scene_intersect_wave<EAGER, DEEP, (WV == 2), false, true>(S, r, RV(1e-4), RT_INF, ht, h,
+            const bool hit = scene_intersect_wave<EAGER, DEEP, (WV == 2), false, true, KA>(S, r, RV(1e-4), RT_INF, ht, h,
                                                                __builtin_amdgcn_read_exec() == ~0ull, cnt);
             cnt.pe(PH_PRIMARY);
             if (!__any(hit)) return background(S);
 #if defined(RT_ABL) && RT_ABL == 5   // diagnostic: primary hit only, no shading
             if (S.n_objs != 12345) return hit ? h.n : background(S);
 #endif
-            const V3 E = shade<EAGER, DEEP, DL, WV>(S, ht, h, normalized(vneg(r.d)), n_occl, cnt, hit);
+            const V3 E = shade<EAGER, DEEP, DL, WV, RT_STD_UO, false, KA>(S, ht, h, normalized(vneg(r.d)), n_occl, cnt, hit);
             return hit ? E : background(S);
         } else {
             if (!scene_intersect<EAGER, DEEP>(S, r, RV(1e-4), RT_INF, ht, h, cnt)) return background(S);

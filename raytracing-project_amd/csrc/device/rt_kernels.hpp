@@ -111,8 +111,33 @@ __device__ __forceinline__ void flush_counters(unsigned long long* ctr, uint32_t
 #define RT_LEAN_WAVES 4
 #endif
 
+// A/B switches of the lean standard kernels' argument re-reads (KA below):
+// the closest-hit / shading queries and the kernel's tail
+// (profiles/sgpr_relief/ab_parts.txt)
+#ifndef RT_KA_SHADE
+#define RT_KA_SHADE 1
+#endif
+#ifndef RT_KA_TAIL
+#define RT_KA_TAIL 1
+#endif
+// The standard kernels' second argument again (scene_again, rt_device.hpp):
+// it follows the DevScene in the kernarg segment.
+static_assert(sizeof(DevScene) % alignof(StdParams) == 0, "StdParams follows DevScene without padding");
+template <bool KA>
+__device__ __forceinline__ decltype(auto) std_again(const StdParams& P, int at) {
+    if constexpr (KA) {
+        StdParams L = args_again<StdParams>(sizeof(DevScene), at);
+        L.fb = global_table(L.fb), L.counters = global_table(L.counters);
+        return L;
+    } else {
+        return (P);
+    }
+}
+
 // PL: the plain kernels (CntPlain: no transform / CSG code)
-template <bool E, bool D, bool SEC, bool C, bool DL = true, int WV = 0, bool PL = false>
+// KA: a kernel whose arguments are (DevScene S, StdParams P) handed down as
+// they are (every k_std* kernel); the lean kernels ask for the re-reads
+template <bool E, bool D, bool SEC, bool C, bool DL = true, int WV = 0, bool PL = false, bool KA = false>
 __device__ __forceinline__ void std_body(const DevScene& S, const StdParams& P) {
     static_assert(!(PL && C), "plain kernels do not count");
     const int lane = threadIdx.x & 63;
@@ -135,7 +160,7 @@ __device__ __forceinline__ void std_body(const DevScene& S, const StdParams& P) 
         const double2 j = *reinterpret_cast<const double2*>(P.jit + ((size_t)P.jrow[ri] * P.W + x) * 16 + 2 * s);
         const DRay ray = gen_ray_subpixel(S, x, y, RV(j.x), RV(j.y));
         cnt.pe(PH_SETUP);
-        c = trace<E, D, SEC, DL, WV>(S, ray, ni, no, cnt);
+        c = trace<E, D, SEC, DL, WV, RT_KA_SHADE && KA>(S, ray, ni, no, cnt);
     }
     cnt.pb(PH_TAIL);
     // acc += trace(...) for s = 0..7 in order (tracer.cpp:290-296)
@@ -150,6 +175,9 @@ __device__ __forceinline__ void std_body(const DevScene& S, const StdParams& P) 
         acc.y += cy;
         acc.z += cz;
     }
+    // (P's fields the tail needs, from the kernarg segment: not live across
+    // the trace; the first lane's ray count ties the read to the trace's end)
+    const StdParams& T = std_again<RT_KA_TAIL && KA>(P, (int)__builtin_amdgcn_readfirstlane(ni));
     if (active && s == 0) {
         const real inv = RV(1.0) / (real)8;
         // the pixel's row and column again, from a thread id the compiler
@@ -161,13 +189,13 @@ __device__ __forceinline__ void std_body(const DevScene& S, const StdParams& P) 
         const int wave2 = t >> 6, pix2 = (t & 63) >> 3;
         const int x2 = blockIdx.x * kStdBlockX + (wave2 & 1) * kStdTW + (pix2 % kStdTW);
         const int ri2 = blockIdx.y * kStdBlockY + (wave2 >> 1) * kStdTH + (pix2 / kStdTW);
-        double* o = P.fb + ((size_t)ri2 * P.W + x2) * 3;
+        double* o = T.fb + ((size_t)ri2 * T.W + x2) * 3;
         o[0] = acc.x * inv;
         o[1] = acc.y * inv;
         o[2] = acc.z * inv;
     }
     cnt.pe(PH_TAIL);
-    flush_counters<C, kStdWPB>(P.counters, ni, no, cnt);
+    flush_counters<C, kStdWPB>(T.counters, ni, no, cnt);
 }
 
 // WV: wave-level culling (scene_occluded_wave / scene_intersect_wave), picked
@@ -191,7 +219,7 @@ __global__ __launch_bounds__(kStdThreads) void k_std(DevScene S, StdParams P) {
 template <bool C, int WV, bool PL = false>
 __global__ __launch_bounds__(kStdThreads) __attribute__((amdgpu_waves_per_eu(PL ? RT_PLAIN_LEAN_WAVES : RT_LEAN_WAVES))) void k_std_lean(DevScene S,
                                                                                                        StdParams P) {
-    std_body<false, false, false, C, false, WV, PL>(S, P);
+    std_body<false, false, false, C, false, WV, PL, /*KA=*/!PL>(S, P);
 }
 
 // Reflection / refraction with wave-level culling (trace_wave): the wave
