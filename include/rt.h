@@ -72,9 +72,11 @@ extern "C" {
                                rt_hit, are pure additions, as are the radiance queries
                                rt_query_radiance / rt_query_radiance_device, the
                                shading queries rt_query_shade / rt_query_shade_device,
-                               and the camera rays and sample resolve rt_camera_rays /
+                               the camera rays and sample resolve rt_camera_rays /
                                rt_camera_rays_device / rt_resolve_samples /
-                               rt_resolve_samples_device) */
+                               rt_resolve_samples_device, and the paper-frame links
+                               rt_rays_wo / rt_rays_wo_device / rt_paper_resolve /
+                               rt_paper_resolve_device) */
 
 /* ---------------------------------------------------------------- errors */
 enum rt_status {
@@ -592,6 +594,70 @@ int rt_camera_rays(const rt_camera* cam, int W, int H, int kind, const int32_t* 
  * host form is a plain loop in librt_host.so and needs no device. */
 int rt_resolve_samples_device(const double* rgb_dev, size_t n_pixels, int spp, double* fb_dev, void* hip_stream);
 int rt_resolve_samples(const double* rgb_host, size_t n_pixels, int spp, double* fb_host);
+
+/* ------------------------------------ paper frames from the queries
+ * The two links that make a paper-mode frame (tracer.cpp:258-281) a
+ * composition of the queries, with every buffer on the device:
+ *   paper = rt_paper_resolve(hits, mask, rt_query_shade(hits, rt_rays_wo(rays), mask, miss_rgb = (1,1,1)))
+ *   where (hits, mask) = rt_query_intersect(rays), rays = rt_camera_rays(cam, RT_RAYS_CENTRE).
+ * trace_paper (tracer.cpp:111-120) is the shading of the centre rays' hits on
+ * white; what remains is the stencil of Tracer::get_edge_strength
+ * (tracer.cpp:133-178), get_luminance (:123-125) and apply_crosshatch
+ * (:188-205) over that G-buffer.  Because the camera and the lights are
+ * arguments of the earlier links, a paper frame of the resident scene can be
+ * rendered from any camera and under rt_query_shade's light override, and the
+ * edge strength is an output of its own (an outline pass over any frame).
+ *
+ * rt_rays_wo: wo[3i .. 3i+2] = (-Ray(rays[i].o, rays[i].d).d).normalized(), the
+ * wo that Tracer::trace and trace_paper hand to shade_lambert_phong
+ * (tracer.cpp:30, :115).  The Ray constructor's own normalisation comes first
+ * (core.h:278: a direction of length <= 1e-6, or NaN, becomes (0, 1, 0)), then
+ * Dir3::normalized of the negation.  o, tmin and tmax are NOT READ.  n == 0 is
+ * RT_OK without a launch; a NULL buffer with n > 0, or a wo that overlaps rays,
+ * is RT_ERR_INVALID_ARG.  The device form runs on hip_stream (NULL = the
+ * default stream) of the current device and blocks until done; the host form
+ * is a plain loop in librt_host.so and needs no device. */
+int rt_rays_wo_device(const rt_ray* rays_dev, size_t n, double* wo_dev, void* hip_stream);
+int rt_rays_wo(const rt_ray* rays_host, size_t n, double* wo_host);
+/* rt_paper_resolve: output rows [row0, row0 + n_rows) of a W x H paper frame.
+ * Paper mode does not flip: the output row is y of generate_ray(x, y), so the
+ * rows of rt_camera_rays(..., RT_RAYS_CENTRE, rows) line up as they are.
+ * Input band: hits, hit_mask and rgb hold frame rows [in0, in1) =
+ * [max(0, row0 - 1), min(H, row0 + n_rows + 1)): the band plus the halo rows
+ * that exist inside the frame.  Pixel (x, y) is at index (y - in0)*W + x of
+ * each (rgb: 3 doubles per pixel).  A whole frame is row0 = 0, n_rows = H and
+ * has no halo; the band form tiles a frame whose records exceed a buffer (the
+ * hits of 7680x4320 are 2.1 GB) and splits one over several devices.
+ * edge[(y - row0)*W + x] = get_edge_strength(x, y) from the stored records:
+ * neighbours in the order (-1,0) (1,0) (0,-1) (0,1); one outside W x H is
+ * skipped and not counted as valid; "hits" is hit_mask != 0 (NULL: every entry
+ * is a hit); the 0.9 (hit against miss), 0.6 (min t > 1e-4 and max t / min t >
+ * 3), 0.5 (n . n' < 0.2) and 0.3 (mat != mat' and n . n' < 0.7) rules read t, n
+ * and mat of rt_hit; material identity is the index (-1 equals -1, as the
+ * reference's two null pointers do); the result is halved when fewer than 4
+ * neighbours are valid.  std::min / std::max and every comparison behave as in
+ * the reference on NaN and infinity.  p and front_face are NOT READ.
+ * fb[((y - row0)*W + x)*3 ..] is the pixel of tracer.cpp:266-279 from base =
+ * rgb of the pixel, L = 0.299 r + 0.587 g + 0.114 b (left to right, no
+ * contraction), the edge strength and apply_crosshatch(base, L, x, y).  rgb is
+ * read for every pixel, misses included: the reference's white for a miss is
+ * the caller's miss_rgb = (1, 1, 1) in rt_query_shade.  A NaN luminance takes
+ * no hatch branch and gives white.
+ * Either output may be NULL, but not both; rgb may be NULL only when fb is.
+ * RT_ERR_INVALID_ARG: W <= 0, H <= 0, row0 < 0, n_rows < 0, row0 + n_rows > H,
+ * a NULL hits with n_rows > 0, or an output that overlaps an input; every
+ * argument check comes before any device work.  n_rows == 0 is RT_OK without a
+ * launch.  stats (may be NULL): pixels = n_rows*W, ms_kernel, ms_total, n_gpus
+ * = 1; the ray counts are 0.  The device form uses the current HIP device,
+ * enqueues on hip_stream (NULL = the default stream), waits for an open frame
+ * of the device and blocks until done.  It needs no scene and uploads nothing:
+ * the resident scene copy is left alone.  The host form is a plain loop in
+ * librt_host.so, compiled without FP contraction, and needs no device: it is
+ * the statement of the rules the device form matches bit for bit. */
+int rt_paper_resolve_device(const rt_hit* hits_dev, const uint8_t* hit_mask_dev, const double* rgb_dev, int W, int H,
+                            int row0, int n_rows, double* fb_dev, double* edge_dev, void* hip_stream, rt_stats* stats);
+int rt_paper_resolve(const rt_hit* hits_host, const uint8_t* hit_mask_host, const double* rgb_host, int W, int H,
+                     int row0, int n_rows, double* fb_host, double* edge_host);
 
 /* ------------------------------------------------------------ host I/O */
 /* toByte(v) = round(clamp01(v)*255) (core.h:316), RGB order. */

@@ -16,6 +16,8 @@
 // (The batched ray-query kernels k_query_isect / k_query_occl and their table
 // live in rt_query_kernels.hpp, built in translation units of their own.)
 
+#include "paper_rules.hpp"
+
 namespace RT_NS {
 
 using rtamd::kCounterSlots;
@@ -236,38 +238,16 @@ __global__ __launch_bounds__(kStdThreads) __attribute__((amdgpu_waves_per_eu(PL 
     std_body<false, false, true, C, false, WV, PL>(S, P);   // (no directional lights: those scenes take D)
 }
 
-// apply_crosshatch (tracer.cpp:188-205) in two halves.  Its FP64 part - the
-// luminance tests - depends on the pixel's own shading only, so the primary
-// pass reduces it to a band (0: lum < 0.15, black; 1..6: the darkness branch
-// taken; 7: no branch, white; a NaN luminance takes none, as in the
-// reference) stored with the material (4 bits instead of an 8-byte
-// luminance); the finish pass applies the band's (x, y) pattern.  C++ '%'
-// truncation toward zero.
-__device__ __forceinline__ int hatch_band(real lum) {
-    if (lum < RV(0.15)) return 0;
-    const real darkness = RV(1.0) - lum;
-    if (darkness > RV(0.8)) return 1;
-    if (darkness > RV(0.65)) return 2;
-    if (darkness > RV(0.5)) return 3;
-    if (darkness > RV(0.35)) return 4;
-    if (darkness > RV(0.2)) return 5;
-    if (darkness > RV(0.12)) return 6;
-    return 7;
-}
-__device__ __forceinline__ real crosshatch(int band, int x, int y) {
-    if (band == 0) return RV(0.0);
-    const bool diag1 = ((x + y) % 4) < 1;
-    const bool diag2 = ((x - y) % 4) < 1;
-    const bool horizontal = (y % 4) < 1;
-    bool draw = false;
-    if (band == 1) draw = (diag1 && diag2) || horizontal;
-    else if (band == 2) draw = (diag1 && diag2) || (horizontal && ((x + y) % 3 == 0));
-    else if (band == 3) draw = (diag1 && diag2) || (horizontal && ((x + y) % 4 == 0));
-    else if (band == 4) draw = diag1 || (horizontal && ((x + y) % 3 == 0));
-    else if (band == 5) draw = diag1;
-    else if (band == 6) draw = diag1 && ((x + y) % 8) < 2;
-    return draw ? RV(0.0) : RV(1.0);
-}
+// apply_crosshatch (tracer.cpp:188-205) in two halves (paper_rules.hpp: the one
+// copy of paper mode's pixel rules, shared with k_paper_resolve and the host
+// form of rt_paper_resolve).  Its FP64 part - the luminance tests - depends
+// on the pixel's own shading only, so the primary pass reduces it to a band
+// (0: lum < 0.15, black; 1..6: the darkness branch taken; 7: no branch,
+// white; a NaN luminance takes none, as in the reference) stored with the
+// material (4 bits instead of an 8-byte luminance); the finish pass applies
+// the band's (x, y) pattern.
+__device__ __forceinline__ int hatch_band(real lum) { return rtamd::paper::hatch_band<real>(lum); }
+__device__ __forceinline__ real crosshatch(int band, int x, int y) { return rtamd::paper::crosshatch<real>(band, x, y); }
 // material slot: material (>= -3) in the low 24 bits, band in bits 24-27
 __device__ __forceinline__ int paper_mat_pack(int mat, int band) { return (mat & 0xffffff) | (band << 24); }
 __device__ __forceinline__ int paper_mat(int slot) {   // (sign-extends the material's 24 bits)
@@ -379,7 +359,7 @@ __device__ __forceinline__ void paper_primary_body(const DevScene& S, const Pape
                                                                                      cnt, sh && hits);
         if (sh) {
             if (!hits) base = v3(RV(1.0), RV(1.0), RV(1.0));
-            band = hatch_band(RV(0.299) * base.x + RV(0.587) * base.y + RV(0.114) * base.z);
+            band = hatch_band(rtamd::paper::luminance<real>(base.x, base.y, base.z));
         }
     }
     // the material slot: the material (kPaperMiss for no hit: the finish
@@ -425,43 +405,13 @@ template <bool CODES>
 __device__ __forceinline__ void paper_pixel(const PaperParams& P, int x, int y, int ri, int cm, real ct, V3 cn,
                                             int cband, const int (&nm)[4], const real (&nt)[4], const real (&nnx)[4],
                                             const real (&nny)[4], const real (&nnz)[4]) {
-    const bool ch = cm != kPaperMiss;
-    // get_edge_strength (tracer.cpp:133-178)
-    real maxEdge = RV(0.0);
-    int eidx = 0;   // index of maxEdge in {0, 0.3, 0.5, 0.6, 0.9} (rtamd::paper_code)
-    int valid = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int dx = (i == 0) ? -1 : (i == 1) ? 1 : 0;
-        const int dy = (i == 2) ? -1 : (i == 3) ? 1 : 0;
-        const int nxp = x + dx, nyp = y + dy;
-        if (nxp < 0 || nxp >= P.W || nyp < 0 || nyp >= P.H) continue;
-        ++valid;
-        const bool nh = nm[i] != kPaperMiss;
-        if (ch != nh) {
-            maxEdge = dmax(maxEdge, RV(0.9));
-            eidx = max(eidx, 4);
-            continue;
-        }
-        if (ch && nh) {
-            const real minD = dmin(ct, nt[i]), maxD = dmax(ct, nt[i]);
-            if (minD > RV(1e-4) && maxD / minD > RV(3.0)) {
-                maxEdge = dmax(maxEdge, RV(0.6));
-                eidx = max(eidx, 3);
-            }
-            const real nd = dot3(cn, v3(nnx[i], nny[i], nnz[i]));
-            if (nd < RV(0.2)) {
-                maxEdge = dmax(maxEdge, RV(0.5));
-                eidx = max(eidx, 2);
-            }
-            if (cm != nm[i] && nd < RV(0.7)) {
-                maxEdge = dmax(maxEdge, RV(0.3));
-                eidx = max(eidx, 1);
-            }
-        }
-    }
-    if (valid < 4) maxEdge *= RV(0.5);
-    const real edge = maxEdge;
+    // get_edge_strength (tracer.cpp:133-178): hit / miss is the material slot
+    // against kPaperMiss, a neighbour outside the frame is not counted
+    const bool nv[4] = {x - 1 >= 0, x + 1 < P.W, y - 1 >= 0, y + 1 < P.H};
+    const bool nh[4] = {nm[0] != kPaperMiss, nm[1] != kPaperMiss, nm[2] != kPaperMiss, nm[3] != kPaperMiss};
+    int eidx, valid;   // index of the strength in {0, 0.3, 0.5, 0.6, 0.9} (rtamd::paper_code); neighbours counted
+    const real edge = rtamd::paper::edge_strength<real>(cm != kPaperMiss, ct, cn.x, cn.y, cn.z, cm, nv, nh, nt, nnx, nny,
+                                                        nnz, nm, eidx, valid);
     if constexpr (CODES) {
         // distributed frames: the pixel's place in the output alphabet
         // (rtamd::paper_code), decoded bit-exactly on the root after the gather
@@ -469,21 +419,8 @@ __device__ __forceinline__ void paper_pixel(const PaperParams& P, int x, int y, 
         P.code[(size_t)ri * P.W + x] = (uint8_t)(eidx | (valid < 4 ? 8 : 0) | (h ? 16 : 0));
         return;
     }
-    V3 o;
-    if (edge > RV(0.8)) {
-        o = v3(RV(0.0), RV(0.0), RV(0.0));
-    } else if (edge > RV(0.5)) {
-        o = v3(RV(0.2), RV(0.2), RV(0.2));
-    } else {
-        const real h = crosshatch(cband, x, y);
-        o = v3(h, h, h);
-        if (edge > RV(0.3)) {
-            const real darken = (edge - RV(0.3)) * RV(0.4);
-            o.x *= (RV(1.0) - darken);
-            o.y *= (RV(1.0) - darken);
-            o.z *= (RV(1.0) - darken);
-        }
-    }
+    const real v = rtamd::paper::pixel_value<real>(edge, cband, x, y);
+    const V3 o = v3(v, v, v);
     double* dst = P.fb + ((size_t)ri * P.W + x) * 3;
     dst[0] = o.x;
     dst[1] = o.y;

@@ -47,6 +47,7 @@
 #include "mt_poly.hpp"
 #include "rt.h"
 #include "rt_camera.hpp"
+#include "rt_paper.hpp"
 #include "rt_devbuf.hpp"
 #include "rt_launch.hpp"
 #include "rt_internal.hpp"
@@ -1684,6 +1685,75 @@ extern "C" int rt_resolve_samples_device(const double* rgb_dev, size_t n_pixels,
     P.fb = fb_dev;
     HIP_TRY(rtd::launch_resolve_samples((hipStream_t)hip_stream, P));
     HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+    return RT_OK;
+}
+
+extern "C" int rt_rays_wo_device(const rt_ray* rays_dev, size_t n, double* wo_dev, void* hip_stream) {
+    const int rc = rtamd::rays_wo_check("rt_rays_wo_device", rays_dev, n, wo_dev);
+    if (rc != RT_OK || !n) return rc;
+    rtamd::RaysWoParams P;
+    P.rays = rays_dev;
+    P.n = n;
+    P.wo = wo_dev;
+    HIP_TRY(rtd::launch_rays_wo((hipStream_t)hip_stream, P));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+    return RT_OK;
+}
+
+// rt_paper_resolve_device: k_paper_resolve (rt_paper_f64.hip) over the
+// caller's device buffers.  No scene: nothing is uploaded and the resident
+// scene copy is not touched.  Holds the workspace lock like a frame (its
+// events time the kernel), and returns with the stream drained.
+extern "C" int rt_paper_resolve_device(const rt_hit* hits_dev, const uint8_t* hit_mask_dev, const double* rgb_dev, int W,
+                                       int H, int row0, int n_rows, double* fb_dev, double* edge_dev, void* hip_stream,
+                                       rt_stats* stats) {
+    const auto t_start = SClock::now();
+    const int rc = rtamd::paper_resolve_check("rt_paper_resolve_device", hits_dev, hit_mask_dev, rgb_dev, W, H, row0,
+                                              n_rows, fb_dev, edge_dev);
+    if (rc != RT_OK) return rc;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->n_gpus = 1;
+    }
+    if (n_rows == 0) return RT_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        rtamd::set_last_error("rt_paper_resolve_device: no HIP device available");
+        return RT_ERR_NO_DEVICE;
+    }
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    Workspace& ws = workspace(dev);
+    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
+    struct Drain {
+        hipStream_t st;
+        ~Drain() { (void)hipStreamSynchronize(st); }
+    } drain{st};
+    if (!ws.ev[0]) {
+        rtamd::SetupTimer tm(rtamd::kSetupStreams);
+        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
+    }
+    rtamd::PaperResolveParams P;
+    P.hits = hits_dev;
+    P.mask = hit_mask_dev;
+    P.rgb = rgb_dev;
+    P.W = W;
+    P.H = H;
+    P.row0 = row0;
+    P.n_rows = n_rows;
+    P.fb = fb_dev;
+    P.edge = edge_dev;
+    HIP_TRY(hipEventRecord(ws.ev[1], st));
+    HIP_TRY(rtd::launch_paper_resolve(st, P));
+    HIP_TRY(hipEventRecord(ws.ev[2], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (stats) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) stats->ms_kernel = ms;
+        stats->pixels = (uint64_t)n_rows * W;
+        stats->ms_total = ms_since(t_start);
+    }
     return RT_OK;
 }
 

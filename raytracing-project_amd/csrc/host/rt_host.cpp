@@ -7,6 +7,7 @@
 #include <new>
 #include <string>
 
+#include "paper_rules.hpp"
 #include "rt.h"
 #include "rt_internal.hpp"
 #include "scene_ir.hpp"
@@ -52,6 +53,119 @@ extern "C" int rt_resolve_samples(const double* rgb, size_t n_pixels, int spp, d
             double acc = 0.0;
             for (int s = 0; s < spp; ++s) acc += src[3 * s + c];
             fb[3 * p + c] = acc * inv;
+        }
+    }
+    return RT_OK;
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return a && b && na && nb && pb < pa + na && pa < pb + nb;
+}
+
+int rtamd::rays_wo_check(const char* what, const rt_ray* rays, size_t n, const double* wo) {
+    const auto fail = [what](const char* msg) {
+        set_last_error(std::string(what) + ": " + msg);
+        return (int)RT_ERR_INVALID_ARG;
+    };
+    if (!n) return RT_OK;
+    if (!rays || !wo) return fail("NULL buffer");
+    if (ranges_overlap(rays, n * sizeof(rt_ray), wo, n * 3 * sizeof(double))) return fail("wo overlaps rays");
+    return RT_OK;
+}
+
+// Dir3::normalized (core.h:95-101)
+static void normalized3(const double v[3], double out[3]) {
+    const double L = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (L > 1e-6) {
+        out[0] = v[0] / L;
+        out[1] = v[1] / L;
+        out[2] = v[2] / L;
+    } else {
+        out[0] = 0.0;
+        out[1] = 1.0;
+        out[2] = 0.0;
+    }
+}
+
+// wo = (-Ray(o, d).d).normalized() (tracer.cpp:30, :115; Ray::Ray core.h:278)
+extern "C" int rt_rays_wo(const rt_ray* rays, size_t n, double* wo) {
+    const int rc = rtamd::rays_wo_check("rt_rays_wo", rays, n, wo);
+    if (rc != RT_OK) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        double d[3];
+        normalized3(rays[i].d, d);
+        const double neg[3] = {-d[0], -d[1], -d[2]};
+        normalized3(neg, wo + 3 * i);
+    }
+    return RT_OK;
+}
+
+int rtamd::paper_resolve_check(const char* what, const rt_hit* hits, const uint8_t* mask, const double* rgb, int W, int H,
+                               int row0, int n_rows, const double* fb, const double* edge) {
+    const auto fail = [what](const char* msg) {
+        set_last_error(std::string(what) + ": " + msg);
+        return (int)RT_ERR_INVALID_ARG;
+    };
+    if (W <= 0 || H <= 0) return fail("W and H must be > 0");
+    if (row0 < 0 || n_rows < 0 || n_rows > H - row0) return fail("rows [row0, row0 + n_rows) must lie in [0, H)");
+    if (n_rows == 0) return RT_OK;
+    if (!hits) return fail("hits is NULL");
+    if (!fb && !edge) return fail("fb and edge are both NULL");
+    if (fb && !rgb) return fail("rgb is NULL with an fb");
+    const int in0 = row0 > 0 ? row0 - 1 : 0, in1 = row0 + n_rows < H ? row0 + n_rows + 1 : H;
+    const size_t n_in = (size_t)(in1 - in0) * (size_t)W, n_out = (size_t)n_rows * (size_t)W;
+    const void* outs[2] = {fb, edge};
+    const size_t out_bytes[2] = {n_out * 3 * sizeof(double), n_out * sizeof(double)};
+    for (int o = 0; o < 2; ++o) {
+        if (ranges_overlap(outs[o], out_bytes[o], hits, n_in * sizeof(rt_hit)) ||
+            ranges_overlap(outs[o], out_bytes[o], mask, n_in) ||
+            ranges_overlap(outs[o], out_bytes[o], rgb, n_in * 3 * sizeof(double)))
+            return fail("an output overlaps an input");
+    }
+    if (ranges_overlap(fb, out_bytes[0], edge, out_bytes[1])) return fail("fb overlaps edge");
+    return RT_OK;
+}
+
+// The paper pixel of tracer.cpp:258-281 over stored records, by the rules of
+// paper_rules.hpp.  Compiled, like the reference, without FMA contraction.
+extern "C" int rt_paper_resolve(const rt_hit* hits, const uint8_t* mask, const double* rgb, int W, int H, int row0,
+                                int n_rows, double* fb, double* edge) {
+    const int rc = rtamd::paper_resolve_check("rt_paper_resolve", hits, mask, rgb, W, H, row0, n_rows, fb, edge);
+    if (rc != RT_OK) return rc;
+    namespace pr = rtamd::paper;
+    const int in0 = row0 > 0 ? row0 - 1 : 0;
+    static const int dx[4] = {-1, 1, 0, 0}, dy[4] = {0, 0, -1, 1};
+    for (int y = row0; y < row0 + n_rows; ++y) {
+        for (int x = 0; x < W; ++x) {
+            const size_t ci = (size_t)(y - in0) * (size_t)W + (size_t)x;
+            const rt_hit& c = hits[ci];
+            bool nv[4], nh[4];
+            double nt[4], nnx[4], nny[4], nnz[4];
+            int nm[4];
+            for (int i = 0; i < 4; ++i) {
+                const int nx = x + dx[i], ny = y + dy[i];
+                nv[i] = !(nx < 0 || nx >= W || ny < 0 || ny >= H);
+                // (a skipped neighbour's values are not looked at: the centre's stand in)
+                const size_t ni = nv[i] ? (size_t)(ny - in0) * (size_t)W + (size_t)nx : ci;
+                const rt_hit& h = hits[ni];
+                nh[i] = mask ? mask[ni] != 0 : true;
+                nt[i] = h.t;
+                nnx[i] = h.n[0];
+                nny[i] = h.n[1];
+                nnz[i] = h.n[2];
+                nm[i] = h.mat;
+            }
+            int eidx, valid;
+            const double e = pr::edge_strength<double>(mask ? mask[ci] != 0 : true, c.t, c.n[0], c.n[1], c.n[2], c.mat, nv,
+                                                       nh, nt, nnx, nny, nnz, nm, eidx, valid);
+            const size_t oi = (size_t)(y - row0) * (size_t)W + (size_t)x;
+            if (edge) edge[oi] = e;
+            if (fb) {
+                const double* base = rgb + 3 * ci;
+                const double v = pr::pixel_value<double>(e, pr::hatch_band<double>(pr::luminance<double>(base[0], base[1], base[2])), x, y);
+                fb[3 * oi] = fb[3 * oi + 1] = fb[3 * oi + 2] = v;
+            }
         }
     }
     return RT_OK;

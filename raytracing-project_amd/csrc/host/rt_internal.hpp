@@ -17,6 +17,12 @@ bool node_depth_ok(const rt_scene_desc& d, int idx, int level, int* maxdepth);
 // Process-unique id of a scene handle (scenes are immutable after creation,
 // so a device copy keyed by it never goes stale).
 uint64_t scene_uid(const rt_scene* s);
+// The argument checks of rt_paper_resolve and rt_paper_resolve_device (one
+// copy: addresses only, nothing is dereferenced).  RT_OK, or
+// RT_ERR_INVALID_ARG with the message left in rt_last_error() under `what`.
+int paper_resolve_check(const char* what, const rt_hit* hits, const uint8_t* mask, const double* rgb, int W, int H,
+                        int row0, int n_rows, const double* fb, const double* edge);
+int rays_wo_check(const char* what, const rt_ray* rays, size_t n, const double* wo);
 // librtamd: free every per-device workspace of slot >= min_slot (rt_shutdown:
 // all of them); returns an rt_status.
 int release_device_workspaces(int min_slot = 0);

@@ -166,6 +166,10 @@ def host_lib():
         lib.rt_write_png.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]
         if hasattr(lib, "rt_resolve_samples"):   # (absent only in builds of older sources)
             lib.rt_resolve_samples.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        if hasattr(lib, "rt_paper_resolve"):   # (likewise)
+            lib.rt_rays_wo.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+            lib.rt_paper_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p]
         _host = lib
     return _host
 
@@ -220,6 +224,10 @@ def amd_lib():
                                                   C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
             lib.rt_resolve_samples_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
             lib.rt_test_camera_chunk_rays.argtypes = [C.c_size_t]
+        if hasattr(lib, "rt_paper_resolve_device"):   # (likewise)
+            lib.rt_rays_wo_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+            lib.rt_paper_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.rt_device_count.restype = C.c_int
         lib.rt_render_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                         C.POINTER(Stats)]
@@ -784,6 +792,23 @@ def query_occluded(scene: Scene, origins, dirs, tmin=1e-4, tmax=np.inf, flags: i
     return occ.astype(bool)
 
 
+def query_intersect_device(scene: Scene, rays_dev: DeviceBuffer, n: int, hits_dev: DeviceBuffer,
+                           mask_dev: DeviceBuffer | None, flags: int = RT_FLAG_NONE, stream: Stream | None = None,
+                           stats: Stats | None = None) -> None:
+    """rt_query_intersect_device: the first n rt_ray records of rays_dev into
+    the first n rt_hit records of hits_dev (and n flag bytes of mask_dev, when
+    given), on `stream` (None: the default stream)."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize or hits_dev.nbytes < n * HIT_DTYPE.itemsize \
+            or (mask_dev is not None and mask_dev.nbytes < n):
+        raise ValueError("query_intersect_device: a buffer is too small for n rays")
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_intersect_device(scene.handle, rays_dev.ptr, n, flags, hits_dev.ptr,
+                                             mask_dev.ptr if mask_dev is not None else None,
+                                             stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
 def query_kernel_name(scene: Scene, kind: int, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
     """rt_test_query_kernel_name: (status, "ns::kernel") of the kernel a query
     of kind 0 (intersect) / 1 (occluded) launches.  Host only."""
@@ -1005,6 +1030,81 @@ def resolve_samples_device(rgb_dev: DeviceBuffer, n_pixels: int, spp: int, fb_de
     if n_pixels < 0 or rgb_dev.nbytes < n_pixels * max(spp, 0) * 24 or fb_dev.nbytes < n_pixels * 24:
         raise ValueError("resolve_samples_device: a buffer is too small")
     rc = amd_lib().rt_resolve_samples_device(rgb_dev.ptr, n_pixels, spp, fb_dev.ptr, stream.handle if stream else None)
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def rays_wo(rays) -> np.ndarray:
+    """rt_rays_wo (host): wo = (-Ray(o, d).d).normalized() of every rt_ray of a
+    RAY_DTYPE array, as an array of its shape + (3,): what Tracer::trace and
+    trace_paper hand to shade_lambert_phong, so query_shade's wo for the hits
+    of these rays."""
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    wo = np.zeros(rays.shape + (3,), dtype=np.float64)
+    rc = host_lib().rt_rays_wo(rays.ctypes.data_as(C.c_void_p), rays.size, wo.ctypes.data_as(C.c_void_p))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return wo
+
+
+def rays_wo_device(rays_dev: DeviceBuffer, n: int, wo_dev: DeviceBuffer, stream: Stream | None = None) -> None:
+    """rt_rays_wo_device: the first n rt_ray records of rays_dev into the first
+    3n doubles of wo_dev, on `stream` (None: the default stream)."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize or wo_dev.nbytes < n * 24:
+        raise ValueError("rays_wo_device: a buffer is too small for n rays")
+    rc = amd_lib().rt_rays_wo_device(rays_dev.ptr, n, wo_dev.ptr, stream.handle if stream else None)
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def paper_band(H: int, row0: int, n_rows: int) -> tuple[int, int]:
+    """The frame rows [in0, in1) that paper_resolve's inputs hold for output
+    rows [row0, row0 + n_rows): the band and the halo rows inside the frame."""
+    return max(0, row0 - 1), min(H, row0 + n_rows + 1)
+
+
+def paper_resolve(hits, mask, rgb, W: int, H: int, row0: int = 0, n_rows: int | None = None, want_edge: bool = False):
+    """rt_paper_resolve (host): output rows [row0, row0 + n_rows) (None: to the
+    last row) of the W x H paper frame whose G-buffer rows paper_band(H, row0,
+    n_rows) are hits (HIT_DTYPE), mask (bytes, or None: all hits) and rgb (the
+    shading on white, 3 doubles a pixel).  Returns fb (n_rows, W, 3), or (fb,
+    edge (n_rows, W)) with want_edge."""
+    if n_rows is None:
+        n_rows = H - row0
+    in0, in1 = paper_band(H, row0, n_rows)
+    n_in = max(in1 - in0, 0) * max(W, 0)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    if hits.size != n_in or rgb.size != 3 * n_in or (m is not None and m.size != n_in):
+        raise ValueError(f"paper_resolve: inputs must hold rows [{in0}, {in1}) of width {W}")
+    fb = np.zeros((max(n_rows, 0), max(W, 0), 3), dtype=np.float64)
+    edge = np.zeros((max(n_rows, 0), max(W, 0)), dtype=np.float64) if want_edge else None
+    rc = host_lib().rt_paper_resolve(hits.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p) if m is not None else None,
+                                     rgb.ctypes.data_as(C.c_void_p), W, H, row0, n_rows, fb.ctypes.data_as(C.c_void_p),
+                                     edge.ctypes.data_as(C.c_void_p) if want_edge else None)
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return (fb, edge) if want_edge else fb
+
+
+def paper_resolve_device(hits_dev: DeviceBuffer, mask_dev: DeviceBuffer | None, rgb_dev: DeviceBuffer | None, W: int,
+                         H: int, row0: int, n_rows: int, fb_dev: DeviceBuffer | None,
+                         edge_dev: DeviceBuffer | None = None, stream: Stream | None = None,
+                         stats: Stats | None = None) -> None:
+    """rt_paper_resolve_device: the same from device buffers holding rows
+    paper_band(H, row0, n_rows), into the first n_rows*W colours of fb_dev and
+    / or the first n_rows*W doubles of edge_dev, on `stream`."""
+    in0, in1 = paper_band(H, row0, n_rows)
+    n_in, n_out = max(in1 - in0, 0) * max(W, 0), max(n_rows, 0) * max(W, 0)
+    if hits_dev.nbytes < n_in * HIT_DTYPE.itemsize or (mask_dev is not None and mask_dev.nbytes < n_in) \
+            or (rgb_dev is not None and rgb_dev.nbytes < n_in * 24) or (fb_dev is not None and fb_dev.nbytes < n_out * 24) \
+            or (edge_dev is not None and edge_dev.nbytes < n_out * 8):
+        raise ValueError("paper_resolve_device: a buffer is too small")
+    st = stats if stats is not None else Stats()
+    opt = lambda b: b.ptr if b is not None else None   # noqa: E731
+    rc = amd_lib().rt_paper_resolve_device(hits_dev.ptr, opt(mask_dev), opt(rgb_dev), W, H, row0, n_rows, opt(fb_dev),
+                                           opt(edge_dev), stream.handle if stream else None, C.byref(st))
     if rc != RT_OK:
         raise RTError(rc, last_error())
 
@@ -1288,12 +1388,65 @@ def oracle_shade(scene: Scene, hits, wo, lights=None):
     return rgb, n_occ
 
 
-def oracle_primary_hits(scene: Scene) -> np.ndarray:
+def oracle_paper_resolve(hits, mask, rgb, W: int, H: int, row0: int, n_rows: int):
+    """(fb (n_rows, W, 3), edge (n_rows, W)) of paper_resolve's inputs: a
+    vectorised numpy restatement of Tracer::get_edge_strength, get_luminance,
+    apply_crosshatch (tracer.cpp:123-205) and the pixel of tracer.cpp:264-279
+    over stored records, statement by statement in float64.  TEST ONLY.
+    std::max(a, b) is a < b ? b : a and std::min(a, b) is b < a ? b : a; '%'
+    truncates toward zero (np.fmod on integers)."""
+    in0, in1 = max(0, row0 - 1), min(H, row0 + n_rows + 1)
+    hits = np.asarray(hits, dtype=HIT_DTYPE).reshape(in1 - in0, W)
+    rgb = np.asarray(rgb, dtype=np.float64).reshape(in1 - in0, W, 3)
+    hit = np.ones((in1 - in0, W), dtype=bool) if mask is None else np.asarray(mask).reshape(in1 - in0, W) != 0
+    smax = lambda a, b: np.where(a < b, b, a)   # noqa: E731
+    smin = lambda a, b: np.where(b < a, b, a)   # noqa: E731
+    ys, xs = np.meshgrid(np.arange(row0, row0 + n_rows), np.arange(W), indexing="ij")
+    at = lambda a, y, x: a[y - in0, x]   # noqa: E731
+    ch, ct, cn, cm = at(hit, ys, xs), at(hits["t"], ys, xs), at(hits["n"], ys, xs), at(hits["mat"], ys, xs)
+    max_edge = np.zeros((n_rows, W))
+    valid = np.zeros((n_rows, W), dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for dx, dy in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+            nx, ny = xs + dx, ys + dy
+            ok = ~((nx < 0) | (nx >= W) | (ny < 0) | (ny >= H))   # tracer.cpp:151
+            nx, ny = np.where(ok, nx, xs), np.where(ok, ny, ys)
+            valid += ok
+            nh, nt, nn, nm = at(hit, ny, nx), at(hits["t"], ny, nx), at(hits["n"], ny, nx), at(hits["mat"], ny, nx)
+            differ = ok & (ch != nh)
+            max_edge = np.where(differ, smax(max_edge, 0.9), max_edge)
+            both = ok & ~differ & ch & nh
+            min_d, max_d = smin(ct, nt), smax(ct, nt)
+            depth = both & (min_d > 1e-4) & (max_d / min_d > 3.0)
+            max_edge = np.where(depth, smax(max_edge, 0.6), max_edge)
+            nd = cn[..., 0] * nn[..., 0] + cn[..., 1] * nn[..., 1] + cn[..., 2] * nn[..., 2]
+            max_edge = np.where(both & (nd < 0.2), smax(max_edge, 0.5), max_edge)
+            max_edge = np.where(both & (cm != nm) & (nd < 0.7), smax(max_edge, 0.3), max_edge)
+        edge = np.where(valid < 4, max_edge * 0.5, max_edge)
+        base = at(rgb, ys, xs)
+        lum = 0.299 * base[..., 0] + 0.587 * base[..., 1] + 0.114 * base[..., 2]
+        darkness = 1.0 - lum
+        diag1 = np.fmod(xs + ys, 4) < 1
+        diag2 = np.fmod(xs - ys, 4) < 1
+        horizontal = np.fmod(ys, 4) < 1
+        draw = np.select(
+            [darkness > 0.8, darkness > 0.65, darkness > 0.5, darkness > 0.35, darkness > 0.2, darkness > 0.12],
+            [(diag1 & diag2) | horizontal, (diag1 & diag2) | (horizontal & (np.fmod(xs + ys, 3) == 0)),
+             (diag1 & diag2) | (horizontal & (np.fmod(xs + ys, 4) == 0)), diag1 | (horizontal & (np.fmod(xs + ys, 3) == 0)),
+             diag1, diag1 & (np.fmod(xs + ys, 8) < 2)], False)
+        hatch = np.where(lum < 0.15, 0.0, np.where(draw, 0.0, 1.0))
+        out = np.where(edge > 0.3, hatch * (1.0 - (edge - 0.3) * 0.4), hatch)
+        out = np.where(edge > 0.8, 0.0, np.where(edge > 0.5, 0.2, out))
+    return np.repeat(out[..., None], 3, axis=2), edge
+
+
+def oracle_primary_hits(scene: Scene, W: int | None = None, H: int | None = None) -> np.ndarray:
     """The pixel-centre primary hits of the frame (Camera::generate_ray +
     Scene::intersect(r, 1e-4, inf) through the oracle), one record per pixel:
-    hit (bool), d (the ray direction) and the Hit fields.  TEST ONLY."""
+    hit (bool), d (the ray direction) and the Hit fields.  W x H: the frame
+    (None: the camera's own size).  TEST ONLY."""
     lib = oracle_lib()
-    W, H = scene.width, scene.height
+    W, H = scene.width if W is None else W, scene.height if H is None else H
     dirs = np.zeros((W * H, 3))
     hits = np.zeros(W * H, dtype=HIT_DTYPE)
     ok = np.zeros(W * H, dtype=np.uint8)

@@ -47,10 +47,10 @@ def main():
         "radiance": rtamd.radiance_kernel_name(rec1)[1]}}
     d_rays, d_hits, d_mask = rtamd.DeviceBuffer(n * 64), rtamd.DeviceBuffer(n * 64), rtamd.DeviceBuffer(n)
     d_wo, d_rgb, d_rad = rtamd.DeviceBuffer(n * 24), rtamd.DeviceBuffer(n * 24), rtamd.DeviceBuffer(n * 24)
-    # the pixel-centre camera rays (Camera::generate_ray, camera.h) in frame order,
-    # generated on the device; wo = -d needs one read-back of the directions
+    # the pixel-centre camera rays (Camera::generate_ray, camera.h) in frame order and
+    # their wo = (-d).normalized(), both generated on the device
     assert rtamd.camera_rays_device(sc, W, H, rtamd.RT_RAYS_CENTRE, None, d_rays) == n
-    d_wo.from_host(-d_rays.to_host(np.uint8).view(rtamd.RAY_DTYPE)["d"])
+    rtamd.rays_wo_device(d_rays, n, d_wo)
     st = rtamd.Stats()
     ti, ts, tr = [], [], []
     for k in range(1 + a.reps):   # (one warm-up round)
