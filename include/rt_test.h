@@ -312,9 +312,11 @@ int rt_test_jitter_cache_budget(int64_t bytes);
  * script (jitter_cache.hpp jitter_cache_sim: ops[5 * n_ops] in, out[8 * n_ops]).
  * Returns what it returns, or RT_ERR_INVALID_ARG. */
 int rt_test_jitter_cache_sim(const int64_t* ops, int n_ops, int64_t budget, int64_t* out);
-/* Rays of one staging chunk of rt_camera_rays' host form (default 2^20, the
- * queries' chunk; a chunk is whole rows, at least one): n rays from here on,
- * 0: back to the default.  So that a small frame crosses several chunks.
+/* Items of one staging chunk of the batched calls' host forms (default 2^20):
+ * n from here on, 0: back to the default.  It is one variable of their driver:
+ * rays of rt_camera_rays (a chunk is whole rows, at least one), rays of
+ * rt_query_intersect / rt_query_occluded / rt_query_radiance, hits of
+ * rt_query_shade.  So that a small frame or batch crosses several chunks.
  * Process-wide; host only. */
 int rt_test_camera_chunk_rays(size_t n);
 /* GPU: one simulated rank (rank of world) of a distributed frame on the

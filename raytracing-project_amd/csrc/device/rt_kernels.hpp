@@ -17,6 +17,7 @@
 // live in rt_query_kernels.hpp, built in translation units of their own.)
 
 #include "paper_rules.hpp"
+#include "rt_kernel_table.hpp"
 
 namespace RT_NS {
 
@@ -537,10 +538,9 @@ constexpr size_t kStdPool = pool_bytes(kStdThreads), kPaperPool = pool_bytes(kPa
 // the paper primary's grid from the host's 16x16-pixel units
 inline dim3 pgrid(dim3 g) { return kPaperWPB == 4 ? g : dim3(2 * g.x, 2 * g.y); }
 
-// The trace kernels by variant: one table per mode, each kernel written once
-// with its template arguments spelled out, so that an entry's name is the
-// instantiation as rocprofv3 prints it.  (The untimed k_paper_primary entries
-// leave T at its default: the name rt_test_kernel_name has always reported.)
+// The trace kernels by variant: one table per mode, in the tables' one form
+// (rt_kernel_table.hpp).  (The untimed k_paper_primary entries leave T at its
+// default: the name rt_test_kernel_name has always reported.)
 // Columns: E D SEC C WV PL (T), the KernelVariant fields an entry answers to
 // (frame_plan.hpp pick_variant produces only canonical variants).
 // RT_GENERAL_ONLY (the big-stack build) keeps the general E = D = true rows,
@@ -550,16 +550,10 @@ constexpr unsigned vkey(bool e, bool d, bool sec, bool c, int wv, bool pl, bool 
     return (unsigned)e | (unsigned)d << 1 | (unsigned)sec << 2 | (unsigned)c << 3 | (unsigned)pl << 4 |
            (unsigned)t << 5 | (unsigned)wv << 6;
 }
-template <class P>
-struct KernelRow {
-    unsigned key;
-    void (*fn)(DevScene, P);
-    const char* name;
-};
-#define RT_ROW(e, d, sec, c, wv, pl, t, ...) {vkey(e, d, sec, c, wv, pl, t), __VA_ARGS__, #__VA_ARGS__}
+#define RT_ROW(e, d, sec, c, wv, pl, t, ...) RT_KERNEL_ROW(vkey(e, d, sec, c, wv, pl, t), __VA_ARGS__)
 #define RT_STD(e, d, sec, c, wv, pl, ...) RT_ROW(e, d, sec, c, wv, pl, 0, __VA_ARGS__)
 #define RT_PAP(e, d, c, wv, pl, t, ...) RT_ROW(e, d, 0, c, wv, pl, t, __VA_ARGS__)
-const KernelRow<StdParams> kStdKernels[] = {
+const KernelRow<DevScene, StdParams> kStdKernels[] = {
     RT_STD(1, 1, 0, 0, 0, 0, k_std<true, true, false, false, false>),
     RT_STD(1, 1, 0, 1, 0, 0, k_std<true, true, false, true, false>),
     RT_STD(1, 1, 1, 0, 0, 0, k_std<true, true, true, false, false>),
@@ -591,7 +585,7 @@ const KernelRow<StdParams> kStdKernels[] = {
 #endif
 };
 // (timed launches: never op-counting ones, rt_frame_trace)
-const KernelRow<PaperParams> kPaperKernels[] = {
+const KernelRow<DevScene, PaperParams> kPaperKernels[] = {
     RT_PAP(1, 1, 0, 0, 0, 0, k_paper_primary<true, true, false>),
     RT_PAP(1, 1, 0, 0, 0, 1, k_paper_primary<true, true, false, true>),
     RT_PAP(1, 1, 1, 0, 0, 0, k_paper_primary<true, true, true>),
@@ -626,13 +620,9 @@ const KernelRow<PaperParams> kPaperKernels[] = {
 // drops the CODES rows: paper codes need an FP64 frame (rt_render.hip
 // frame_trace refuses them with RT_FLAG_FP32, and rt_dist.hip gathers doubles
 // from FP32 ranks), so no frame can ask this namespace for them.
-struct FinishRow {
-    bool codes, pair;
-    void (*fn)(PaperParams);
-    const char* name;
-};
-#define RT_FIN(codes, pair, ...) {codes, pair, __VA_ARGS__, #__VA_ARGS__}
-const FinishRow kFinishKernels[] = {
+constexpr unsigned fkey(bool codes, bool pair) { return (unsigned)codes | (unsigned)pair << 1; }
+#define RT_FIN(codes, pair, ...) RT_KERNEL_ROW(fkey(codes, pair), __VA_ARGS__)
+const KernelRow<PaperParams> kFinishKernels[] = {
     RT_FIN(0, 0, k_paper_finish<false, false>),
     RT_FIN(0, 1, k_paper_finish<false, true>),
 #ifndef RT_NO_PAPER_CODES
@@ -642,30 +632,18 @@ const FinishRow kFinishKernels[] = {
 };
 #undef RT_FIN
 
-template <class P, size_t N>
-const KernelRow<P>* find_kernel(const KernelRow<P> (&table)[N], unsigned key) {
-    for (const KernelRow<P>& r : table)
-        if (r.key == key) return &r;
-    return nullptr;
-}
-template <class R, size_t N>
-const char* row_name(const R (&table)[N], int i) {
-    return i >= 0 && i < (int)N ? table[i].name : nullptr;
-}
 // (the standard-mode kernels have no timed build, the paper ones no SEC)
-const KernelRow<StdParams>* std_row(const rtamd::KernelVariant& v) {
+const KernelRow<DevScene, StdParams>* std_row(const rtamd::KernelVariant& v) {
     return find_kernel(kStdKernels, vkey(v.eager, v.deep, v.secondary, v.count_ops, v.wv, v.plain, false));
 }
-const KernelRow<PaperParams>* paper_row(const rtamd::KernelVariant& v) {
+const KernelRow<DevScene, PaperParams>* paper_row(const rtamd::KernelVariant& v) {
     return find_kernel(kPaperKernels, vkey(v.eager, v.deep, false, v.count_ops, v.wv, v.plain, v.timed));
 }
 
-}  // namespace
-
 // Each variant gets its own register allocation.  A variant this namespace
 // has no kernel for is an error, never another kernel.
-hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const SceneView& V, const StdParams& P) {
-    const KernelRow<StdParams>* k = std_row(v);
+hipError_t launch_std(const rtamd::KernelVariant& v, int, dim3, hipStream_t st, const SceneView& V, const StdParams& P) {
+    const KernelRow<DevScene, StdParams>* k = std_row(v);
     if (!k) return hipErrorInvalidDeviceFunction;
     const DevScene S = make_scene(V, v.wv == 2);
     const dim3 grid((P.W + kStdBlockX - 1) / kStdBlockX, (P.n_rows + kStdBlockY - 1) / kStdBlockY);
@@ -674,9 +652,9 @@ hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const Scene
     return hipGetLastError();
 }
 
-hipError_t launch_paper(const rtamd::KernelVariant& v, dim3 grid, hipStream_t st, const SceneView& V,
+hipError_t launch_paper(const rtamd::KernelVariant& v, int, dim3 grid, hipStream_t st, const SceneView& V,
                         const PaperParams& P) {
-    const KernelRow<PaperParams>* k = paper_row(v);
+    const KernelRow<DevScene, PaperParams>* k = paper_row(v);
     if (!k) return hipErrorInvalidDeviceFunction;
     const DevScene S = make_scene(V, v.wv == 2);
     rtamd::note_launch(kNsName, k->name);
@@ -684,28 +662,12 @@ hipError_t launch_paper(const rtamd::KernelVariant& v, dim3 grid, hipStream_t st
     return hipGetLastError();
 }
 
-// The kernel launch_std / launch_paper pick for a variant, and its name
-// (resource queries); {nullptr, nullptr}: none in this namespace.
-rtamd::KernelEntry std_kernel(const rtamd::KernelVariant& v) {
-    const KernelRow<StdParams>* k = std_row(v);
-    return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
-}
-rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v) {
-    const KernelRow<PaperParams>* k = paper_row(v);
-    return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
-}
-
-// The trace kernels' workgroup size and dynamic LDS (resource queries)
-int kernel_block_threads(bool paper) { return paper ? kPaperThreads : kStdThreads; }
-size_t kernel_pool_bytes(bool paper) { return paper ? kPaperPool : kStdPool; }
-
-hipError_t launch_paper_finish(dim3 grid, hipStream_t st, const PaperParams& P) {
+hipError_t launch_paper_finish(const rtamd::KernelVariant&, int, dim3 grid, hipStream_t st, const SceneView&,
+                               const PaperParams& P) {
     // (grid.x covers W pixels one per thread; even W: two per thread; grid.y
     // kFinishRows * kFinishRounds rows per block)
-    const bool codes = P.code != nullptr, pair = P.W % 2 == 0;
-    const FinishRow* k = nullptr;
-    for (const FinishRow& r : kFinishKernels)
-        if (r.codes == codes && r.pair == pair) k = &r;
+    const bool pair = P.W % 2 == 0;
+    const KernelRow<PaperParams>* k = find_kernel(kFinishKernels, fkey(P.code != nullptr, pair));
     if (!k) return hipErrorInvalidDeviceFunction;
     grid.y = (P.n_rows + kFinishRows * kFinishRounds - 1) / (kFinishRows * kFinishRounds);
     if (pair) grid.x = (P.W / 2 + 63) / 64;
@@ -714,10 +676,33 @@ hipError_t launch_paper_finish(dim3 grid, hipStream_t st, const PaperParams& P) 
     return hipGetLastError();
 }
 
-// Row i of this namespace's tables as written above (nullptr past the end):
-// what rt_test_kernel_row enumerates.
+rtamd::KernelEntry std_kernel(const rtamd::KernelVariant& v, int) { return kernel_entry(std_row(v)); }
+rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v, int) { return kernel_entry(paper_row(v)); }
+rtamd::KernelEntry finish_kernel(const rtamd::KernelVariant&, int kind) {
+    return kernel_entry(find_kernel(kFinishKernels, (unsigned)kind));
+}
 const char* std_row_name(int i) { return row_name(kStdKernels, i); }
 const char* paper_row_name(int i) { return row_name(kPaperKernels, i); }
 const char* finish_row_name(int i) { return row_name(kFinishKernels, i); }
+
+}  // namespace
+
+// The tables as the host sees them (rt_launch.hpp): the launcher, the kernel a
+// launch picks for a variant, row i as written above, and the trace kernels'
+// workgroup size and dynamic LDS.  (The finish table's kernel(v, kind): kind
+// is its key, CODES | PAIR << 1.)
+const rtamd::KernelTable<StdParams>& std_table() {
+    static const rtamd::KernelTable<StdParams> t = {launch_std, std_kernel, std_row_name, kStdThreads, kStdPool};
+    return t;
+}
+const rtamd::KernelTable<PaperParams>& paper_table() {
+    static const rtamd::KernelTable<PaperParams> t = {launch_paper, paper_kernel, paper_row_name, kPaperThreads, kPaperPool};
+    return t;
+}
+const rtamd::KernelTable<PaperParams>& finish_table() {
+    static const rtamd::KernelTable<PaperParams> t = {launch_paper_finish, finish_kernel, finish_row_name,
+                                                      64 * kFinishRows, 0};
+    return t;
+}
 
 }  // namespace RT_NS

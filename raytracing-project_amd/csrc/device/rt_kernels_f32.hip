@@ -10,13 +10,3 @@
 #define RT_NO_PAPER_CODES   // (paper codes are FP64 frames only: no CODES finish kernels)
 #include "rt_device.hpp"
 #include "rt_kernels.hpp"
-
-// (no FP32 ray queries: rt_query_kernels.hpp is built for rtd and rtdb only)
-namespace rtf {
-hipError_t launch_query(const rtamd::KernelVariant&, int, hipStream_t, const rtamd::SceneView&,
-                        const rtamd::QueryParams&) {
-    return hipErrorInvalidDeviceFunction;
-}
-rtamd::KernelEntry query_kernel(const rtamd::KernelVariant&, int) { return rtamd::KernelEntry{nullptr, nullptr}; }
-const char* query_row_name(int) { return nullptr; }
-}  // namespace rtf

@@ -1,10 +1,12 @@
 // rt_launch.hpp — what the host side of librtamd hands to the render kernels.
 //
-// The kernels exist twice: namespace rtd (FP64, the parity path) and
-// namespace rtf (FP32, RT_FLAG_FP32, rt_render_f32.hip).  Both are built from
-// rt_device.hpp + rt_kernels.hpp; this header holds the precision-neutral
-// launch interface: device pointers, the camera/medium in double, and the
-// per-launch parameter blocks.
+// The kernels exist per namespace: rtd (FP64, the parity path), rtf (FP32,
+// RT_FLAG_FP32, rt_kernels_f32.hip) and rtdb (FP64 with the big stacks, *_big.hip).
+// All are built from rt_device.hpp + one kernel header; this header holds the
+// precision-neutral launch interface: device pointers, the camera/medium in
+// double, the per-launch parameter blocks, and - at its end - the kernel
+// tables as the host sees them (KernelTable) with the one mapping from a
+// KernelVariant's ns to a namespace (kernel_namespace).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -195,112 +197,115 @@ struct KernelEntry {
 };
 
 // The launch log (rt_test.h rt_test_launch_log; defined in rt_test_hooks.hip):
-// every launcher below reports the row it launches, "ns::name".  While the
-// log is off this is one relaxed atomic load.
+// every launcher reports the row it launches, "ns::name".  While the log is
+// off this is one relaxed atomic load.
 void note_launch(const char* ns, const char* name);
+
+// One kernel table of one namespace as the host sees it (the rows: rt_kernels.hpp,
+// rt_query_kernels.hpp, rt_radiance_kernels.hpp, rt_shade_kernels.hpp, each in
+// the form of rt_kernel_table.hpp and in translation units of its own).
+// kind: the query table's rtamd::kQueryIsect / kQueryOccl; grid: the paper
+// tables' (the host's 16x16-pixel units; the finish pass's x extent); a table
+// without such a column ignores the argument.
+template <class P>
+struct KernelTable {
+    // hipErrorInvalidDeviceFunction: the table has no row for the variant
+    hipError_t (*launch)(const KernelVariant& v, int kind, dim3 grid, hipStream_t st, const SceneView& V, const P& p);
+    KernelEntry (*kernel)(const KernelVariant& v, int kind);   // what launch picks; {nullptr, nullptr}: no row
+    const char* (*row_name)(int i);                            // row i as written, nullptr past the end
+    int block_threads;                                         // its launches' workgroup size
+    size_t pool_bytes;                                         //   and dynamic LDS
+};
+
+// The tables of one namespace.  nullptr: the namespace lacks the family.
+struct KernelNamespace {
+    const char* name;
+    const KernelTable<StdParams>* std;
+    const KernelTable<PaperParams>*paper, *finish;
+    const KernelTable<QueryParams>* query;
+    const KernelTable<RadianceParams>* radiance;
+    const KernelTable<ShadeParams>* shade;
+};
 
 }  // namespace rtamd
 
-// The trace kernels of one namespace (rt_kernels.hpp), by KernelVariant
-// (frame_plan.hpp).  launch_*: hipErrorInvalidDeviceFunction when the
-// namespace has no kernel for the variant.  launch_query / query_kernel: the
-// ray-query kernels (rt_query_kernels.hpp, their own translation units; rtf
-// has none).  launch_radiance / radiance_kernel: the radiance-query kernels
-// (rt_radiance_kernels.hpp, likewise; rtd and rtdb only, rtf defines none).
-// launch_shade / shade_kernel: the shading-query kernels (rt_shade_kernels.hpp,
-// likewise).  *_row_name(i): row i of the namespace's table, nullptr past its
-// end (rt_test_kernel_row, rt_test_radiance_kernel_row, rt_test_shade_kernel_row).
-#define RT_DECLARE_LAUNCHERS(NS)                                                                                  \
-    namespace NS {                                                                                                \
-    hipError_t launch_std(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,               \
-                          const rtamd::StdParams& P);                                                             \
-    hipError_t launch_paper(const rtamd::KernelVariant& v, dim3 grid, hipStream_t st, const rtamd::SceneView& V,  \
-                            const rtamd::PaperParams& P);                                                         \
-    hipError_t launch_paper_finish(dim3 grid, hipStream_t st, const rtamd::PaperParams& P);                       \
-    rtamd::KernelEntry std_kernel(const rtamd::KernelVariant& v);                                                 \
-    rtamd::KernelEntry paper_kernel(const rtamd::KernelVariant& v);                                               \
-    int kernel_block_threads(bool paper);                                                                         \
-    size_t kernel_pool_bytes(bool paper);                                                                         \
-    hipError_t launch_query(const rtamd::KernelVariant& v, int kind, hipStream_t st, const rtamd::SceneView& V,   \
-                            const rtamd::QueryParams& P);                                                         \
-    rtamd::KernelEntry query_kernel(const rtamd::KernelVariant& v, int kind);                                     \
-    const char* std_row_name(int i);                                                                              \
-    const char* paper_row_name(int i);                                                                            \
-    const char* finish_row_name(int i);                                                                           \
-    const char* query_row_name(int i);                                                                            \
-    hipError_t launch_radiance(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,          \
-                               const rtamd::RadianceParams& P);                                                   \
-    rtamd::KernelEntry radiance_kernel(const rtamd::KernelVariant& v);                                            \
-    const char* radiance_row_name(int i);                                                                         \
-    hipError_t launch_shade(const rtamd::KernelVariant& v, hipStream_t st, const rtamd::SceneView& V,             \
-                            const rtamd::ShadeParams& P);                                                         \
-    rtamd::KernelEntry shade_kernel(const rtamd::KernelVariant& v);                                               \
-    const char* shade_row_name(int i);                                                                            \
+// Each namespace's tables, defined next to their rows (functions: a const
+// object with these initialisers would be emitted into the device code too)
+#define RT_DECLARE_TABLES(NS)                                          \
+    namespace NS {                                                     \
+    const rtamd::KernelTable<rtamd::StdParams>& std_table();           \
+    const rtamd::KernelTable<rtamd::PaperParams>& paper_table();       \
+    const rtamd::KernelTable<rtamd::PaperParams>& finish_table();      \
+    const rtamd::KernelTable<rtamd::QueryParams>& query_table();       \
+    const rtamd::KernelTable<rtamd::RadianceParams>& radiance_table(); \
+    const rtamd::KernelTable<rtamd::ShadeParams>& shade_table();       \
     }
-RT_DECLARE_LAUNCHERS(rtd)
-RT_DECLARE_LAUNCHERS(rtf)
-RT_DECLARE_LAUNCHERS(rtdb)
+RT_DECLARE_TABLES(rtd)
+RT_DECLARE_TABLES(rtf)    // (defines the frame tables only)
+RT_DECLARE_TABLES(rtdb)
+#undef RT_DECLARE_TABLES
 
-// The launchers of a variant's namespace (the big-stack build has no finish
-// pass of its own: k_paper_finish reads records only).
 namespace rtamd {
+// KernelVariant::ns -> its namespace: the one place that choice is written.
+// rtf has no query, radiance or shade kernels (no FP32 build of them: the
+// pick_*_variant of those families never pick it); the big-stack build has no
+// finish pass of its own (k_paper_finish reads records only): rtd's.
+inline const KernelNamespace& kernel_namespace(int ns) {
+    static const KernelNamespace k[] = {
+        {"rtd", &rtd::std_table(), &rtd::paper_table(), &rtd::finish_table(), &rtd::query_table(),
+         &rtd::radiance_table(), &rtd::shade_table()},
+        {"rtf", &rtf::std_table(), &rtf::paper_table(), &rtf::finish_table(), nullptr, nullptr, nullptr},
+        {"rtdb", &rtdb::std_table(), &rtdb::paper_table(), &rtd::finish_table(), &rtdb::query_table(),
+         &rtdb::radiance_table(), &rtdb::shade_table()}};
+    static_assert(KernelVariant::kRtd == 0 && KernelVariant::kRtf == 1 && KernelVariant::kRtdb == 2, "k's order");
+    return k[ns == KernelVariant::kRtf || ns == KernelVariant::kRtdb ? ns : KernelVariant::kRtd];
+}
+
+// A launch / the kernel of a variant in table t; a family the namespace lacks
+// answers as a table without the row does.
+template <class P>
+hipError_t launch_in(const KernelTable<P>* t, const KernelVariant& v, int kind, dim3 grid, hipStream_t st,
+                     const SceneView& V, const P& p) {
+    return t ? t->launch(v, kind, grid, st, V, p) : hipErrorInvalidDeviceFunction;
+}
+template <class P>
+KernelEntry kernel_in(const KernelTable<P>* t, const KernelVariant& v, int kind = 0) {
+    return t ? t->kernel(v, kind) : KernelEntry{nullptr, nullptr};
+}
+
+// The launchers of a variant's namespace
 inline hipError_t launch_std(const KernelVariant& v, hipStream_t st, const SceneView& V, const StdParams& P) {
-    return v.ns == KernelVariant::kRtf ? rtf::launch_std(v, st, V, P)
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_std(v, st, V, P) : rtd::launch_std(v, st, V, P);
+    return launch_in(kernel_namespace(v.ns).std, v, 0, dim3(), st, V, P);
 }
 inline hipError_t launch_paper(const KernelVariant& v, dim3 grid, hipStream_t st, const SceneView& V,
                                const PaperParams& P) {
-    return v.ns == KernelVariant::kRtf ? rtf::launch_paper(v, grid, st, V, P)
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_paper(v, grid, st, V, P)
-                                                                      : rtd::launch_paper(v, grid, st, V, P);
+    return launch_in(kernel_namespace(v.ns).paper, v, 0, grid, st, V, P);
 }
-inline hipError_t launch_paper_finish(const KernelVariant& v, dim3 grid, hipStream_t st, const PaperParams& P) {
-    return v.ns == KernelVariant::kRtf ? rtf::launch_paper_finish(grid, st, P) : rtd::launch_paper_finish(grid, st, P);
-}
-// The variant's trace kernel of `mode` ({nullptr, nullptr}: none), and its launch shape
-inline KernelEntry trace_kernel(const KernelVariant& v, bool paper) {
-    if (v.ns == KernelVariant::kRtf) return paper ? rtf::paper_kernel(v) : rtf::std_kernel(v);
-    if (v.ns == KernelVariant::kRtdb) return paper ? rtdb::paper_kernel(v) : rtdb::std_kernel(v);
-    return paper ? rtd::paper_kernel(v) : rtd::std_kernel(v);
+inline hipError_t launch_paper_finish(const KernelVariant& v, dim3 grid, hipStream_t st, const SceneView& V,
+                                      const PaperParams& P) {
+    return launch_in(kernel_namespace(v.ns).finish, v, 0, grid, st, V, P);
 }
 inline hipError_t launch_query(const KernelVariant& v, int kind, hipStream_t st, const SceneView& V,
                                const QueryParams& P) {
-    return v.ns == KernelVariant::kRtf ? rtf::launch_query(v, kind, st, V, P)
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_query(v, kind, st, V, P)
-                                                                      : rtd::launch_query(v, kind, st, V, P);
+    return launch_in(kernel_namespace(v.ns).query, v, kind, dim3(), st, V, P);
 }
-inline KernelEntry query_kernel(const KernelVariant& v, int kind) {
-    return v.ns == KernelVariant::kRtf ? rtf::query_kernel(v, kind)
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::query_kernel(v, kind) : rtd::query_kernel(v, kind);
-}
-// (pick_radiance_variant never picks rtf: no FP32 radiance queries)
 inline hipError_t launch_radiance(const KernelVariant& v, hipStream_t st, const SceneView& V, const RadianceParams& P) {
-    return v.ns == KernelVariant::kRtf ? hipErrorInvalidDeviceFunction
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_radiance(v, st, V, P)
-                                                                      : rtd::launch_radiance(v, st, V, P);
+    return launch_in(kernel_namespace(v.ns).radiance, v, 0, dim3(), st, V, P);
 }
-inline KernelEntry radiance_kernel(const KernelVariant& v) {
-    return v.ns == KernelVariant::kRtf ? KernelEntry{nullptr, nullptr}
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::radiance_kernel(v) : rtd::radiance_kernel(v);
-}
-// (pick_shade_variant never picks rtf: no FP32 shading queries)
 inline hipError_t launch_shade(const KernelVariant& v, hipStream_t st, const SceneView& V, const ShadeParams& P) {
-    return v.ns == KernelVariant::kRtf ? hipErrorInvalidDeviceFunction
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::launch_shade(v, st, V, P)
-                                                                      : rtd::launch_shade(v, st, V, P);
+    return launch_in(kernel_namespace(v.ns).shade, v, 0, dim3(), st, V, P);
 }
-inline KernelEntry shade_kernel(const KernelVariant& v) {
-    return v.ns == KernelVariant::kRtf ? KernelEntry{nullptr, nullptr}
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::shade_kernel(v) : rtd::shade_kernel(v);
+// The variant's trace kernel of `mode` ({nullptr, nullptr}: none), and its launch shape
+inline KernelEntry trace_kernel(const KernelVariant& v, bool paper) {
+    const KernelNamespace& n = kernel_namespace(v.ns);
+    return paper ? kernel_in(n.paper, v) : kernel_in(n.std, v);
 }
 inline int trace_block_threads(const KernelVariant& v, bool paper) {
-    return v.ns == KernelVariant::kRtf ? rtf::kernel_block_threads(paper)
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::kernel_block_threads(paper)
-                                                                      : rtd::kernel_block_threads(paper);
+    const KernelNamespace& n = kernel_namespace(v.ns);
+    return paper ? n.paper->block_threads : n.std->block_threads;
 }
 inline size_t trace_pool_bytes(const KernelVariant& v, bool paper) {
-    return v.ns == KernelVariant::kRtf ? rtf::kernel_pool_bytes(paper)
-                                       : v.ns == KernelVariant::kRtdb ? rtdb::kernel_pool_bytes(paper)
-                                                                      : rtd::kernel_pool_bytes(paper);
+    const KernelNamespace& n = kernel_namespace(v.ns);
+    return paper ? n.paper->pool_bytes : n.std->pool_bytes;
 }
 }  // namespace rtamd

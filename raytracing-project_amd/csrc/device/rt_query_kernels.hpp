@@ -24,14 +24,14 @@
 // shade and the counter flush use the pool) and no counters: a batch of n rays
 // is n queries.
 
+#include "rt_kernel_table.hpp"
+
 namespace RT_NS {
 
 using rtamd::QueryParams;
 using rtamd::SceneView;
 
 namespace {
-
-constexpr int kQueryThreads = 64;
 
 // ray i of the batch (lanes past its end: the last ray), as Ray(o, d) (core.h:278)
 __device__ __forceinline__ DRay query_ray(const QueryParams& P, size_t i, real& tmin, real& tmax) {
@@ -85,21 +85,14 @@ __global__ __launch_bounds__(kQueryThreads) void k_query_occl(DevScene S, QueryP
     if (active) P.mask[i] = occ ? 1 : 0;
 }
 
-// The query kernels by variant, as the frame kernels' tables (rt_kernels.hpp):
-// each written once with its template arguments spelled out, so that an
-// entry's name is the instantiation as rocprofv3 prints it.  Columns: kind
-// (rtamd::kQueryIsect / kQueryOccl) E D PL.  RT_GENERAL_ONLY (the big-stack
-// build) keeps the general rows.
+// The query kernels by variant, in the tables' one form (rt_kernel_table.hpp).
+// Columns: kind (rtamd::kQueryIsect / kQueryOccl) E D PL.  RT_GENERAL_ONLY (the
+// big-stack build) keeps the general rows.
 constexpr unsigned qkey(int kind, bool e, bool d, bool pl) {
     return (unsigned)kind | (unsigned)e << 1 | (unsigned)d << 2 | (unsigned)pl << 3;
 }
-struct QueryRow {
-    unsigned key;
-    void (*fn)(DevScene, QueryParams);
-    const char* name;
-};
-#define RT_QRY(kind, e, d, pl, ...) {qkey(kind, e, d, pl), __VA_ARGS__, #__VA_ARGS__}
-const QueryRow kQueryKernels[] = {
+#define RT_QRY(kind, e, d, pl, ...) RT_KERNEL_ROW(qkey(kind, e, d, pl), __VA_ARGS__)
+const KernelRow<DevScene, QueryParams> kQueryKernels[] = {
     RT_QRY(0, 1, 1, 0, k_query_isect<true, true, false>),
     RT_QRY(1, 1, 1, 0, k_query_occl<true, true, false>),
 #ifndef RT_GENERAL_ONLY
@@ -113,40 +106,23 @@ const QueryRow kQueryKernels[] = {
 };
 #undef RT_QRY
 
-const QueryRow* query_row(const rtamd::KernelVariant& v, int kind) {
+const KernelRow<DevScene, QueryParams>* query_row(const rtamd::KernelVariant& v, int kind) {
     if (kind != rtamd::kQueryIsect && kind != rtamd::kQueryOccl) return nullptr;
-    const unsigned key = qkey(kind, v.eager, v.deep, v.plain);
-    for (const QueryRow& r : kQueryKernels)
-        if (r.key == key) return &r;
-    return nullptr;
+    return find_kernel(kQueryKernels, qkey(kind, v.eager, v.deep, v.plain));
 }
+
+hipError_t launch_query(const rtamd::KernelVariant& v, int kind, dim3, hipStream_t st, const SceneView& V,
+                        const QueryParams& P) {
+    return launch_lanes(query_row(v, kind), 0, false, st, V, P);
+}
+rtamd::KernelEntry query_kernel(const rtamd::KernelVariant& v, int kind) { return kernel_entry(query_row(v, kind)); }
+const char* query_row_name(int i) { return row_name(kQueryKernels, i); }
 
 }  // namespace
 
-// One launch over the whole batch (P.n > 0, at most 2^31 - 1 waves: the host
-// splits larger batches).  A variant without a row is an error, never another
-// kernel.
-hipError_t launch_query(const rtamd::KernelVariant& v, int kind, hipStream_t st, const SceneView& V,
-                        const QueryParams& P) {
-    const QueryRow* k = query_row(v, kind);
-    if (!k) return hipErrorInvalidDeviceFunction;
-    const size_t waves = (P.n + kQueryThreads - 1) / kQueryThreads;
-    if (!P.n || waves > 0x7fffffffu) return hipErrorInvalidValue;
-    const DevScene S = make_scene(V);
-    rtamd::note_launch(kNsName, k->name);
-    hipLaunchKernelGGL(k->fn, dim3((unsigned)waves), dim3(kQueryThreads), 0, st, S, P);
-    return hipGetLastError();
-}
-
-rtamd::KernelEntry query_kernel(const rtamd::KernelVariant& v, int kind) {
-    const QueryRow* k = query_row(v, kind);
-    return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
-}
-
-// Row i of the query table as written above (nullptr past the end)
-const char* query_row_name(int i) {
-    constexpr int n = (int)(sizeof(kQueryKernels) / sizeof(kQueryKernels[0]));
-    return i >= 0 && i < n ? kQueryKernels[i].name : nullptr;
+const rtamd::KernelTable<QueryParams>& query_table() {
+    static const rtamd::KernelTable<QueryParams> t = {launch_query, query_kernel, query_row_name, kQueryThreads, 0};
+    return t;
 }
 
 }  // namespace RT_NS

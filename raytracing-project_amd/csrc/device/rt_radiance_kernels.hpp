@@ -23,6 +23,8 @@
 // after the last scene read.  Dynamic LDS: pool_bytes(64), shade()'s light
 // cache (wave_pool).
 
+#include "rt_kernel_table.hpp"
+
 namespace RT_NS {
 
 using rtamd::kCounterSlots;
@@ -32,7 +34,6 @@ using rtamd::SceneView;
 
 namespace {
 
-constexpr int kQueryThreads = 64;
 constexpr size_t kRadiancePool = pool_bytes(kQueryThreads);
 
 // The wave's Scene::intersect / Scene::occluded call counts: reduced by
@@ -75,23 +76,17 @@ __global__ __launch_bounds__(kQueryThreads) void k_radiance(DevScene S, Radiance
     flush_ray_counts(P.counters, active ? ni : 0u, active ? no : 0u);
 }
 
-// The radiance kernels by variant, as the query kernels' table: each written
-// once with its template arguments spelled out, so that an entry's name is the
-// instantiation as rocprofv3 prints it.  Columns: E D SEC PL.  The general
-// row traces every scene (with no reflecting or refracting material, or
-// recursion < 2, its loop never descends), so eager scenes have no SEC = false
-// row (frame_plan.hpp pick_radiance_variant never asks for one);
-// RT_GENERAL_ONLY (the big-stack build) keeps that row alone.
+// The radiance kernels by variant, in the tables' one form
+// (rt_kernel_table.hpp).  Columns: E D SEC PL.  The general row traces every
+// scene (with no reflecting or refracting material, or recursion < 2, its loop
+// never descends), so eager scenes have no SEC = false row (frame_plan.hpp
+// pick_radiance_variant never asks for one); RT_GENERAL_ONLY (the big-stack
+// build) keeps that row alone.
 constexpr unsigned rkey(bool e, bool d, bool sec, bool pl) {
     return (unsigned)e | (unsigned)d << 1 | (unsigned)sec << 2 | (unsigned)pl << 3;
 }
-struct RadianceRow {
-    unsigned key;
-    void (*fn)(DevScene, RadianceParams);
-    const char* name;
-};
-#define RT_RAD(e, d, sec, pl, ...) {rkey(e, d, sec, pl), __VA_ARGS__, #__VA_ARGS__}
-const RadianceRow kRadianceKernels[] = {
+#define RT_RAD(e, d, sec, pl, ...) RT_KERNEL_ROW(rkey(e, d, sec, pl), __VA_ARGS__)
+const KernelRow<DevScene, RadianceParams> kRadianceKernels[] = {
     RT_RAD(1, 1, 1, 0, k_radiance<true, true, true, false>),
 #ifndef RT_GENERAL_ONLY
     RT_RAD(0, 1, 1, 0, k_radiance<false, true, true, false>),
@@ -104,38 +99,23 @@ const RadianceRow kRadianceKernels[] = {
 };
 #undef RT_RAD
 
-const RadianceRow* radiance_row(const rtamd::KernelVariant& v) {
-    const unsigned key = rkey(v.eager, v.deep, v.secondary, v.plain);
-    for (const RadianceRow& r : kRadianceKernels)
-        if (r.key == key) return &r;
-    return nullptr;
+const KernelRow<DevScene, RadianceParams>* radiance_row(const rtamd::KernelVariant& v) {
+    return find_kernel(kRadianceKernels, rkey(v.eager, v.deep, v.secondary, v.plain));
 }
+
+hipError_t launch_radiance(const rtamd::KernelVariant& v, int, dim3, hipStream_t st, const SceneView& V,
+                           const RadianceParams& P) {
+    return launch_lanes(radiance_row(v), kRadiancePool, false, st, V, P);
+}
+rtamd::KernelEntry radiance_kernel(const rtamd::KernelVariant& v, int) { return kernel_entry(radiance_row(v)); }
+const char* radiance_row_name(int i) { return row_name(kRadianceKernels, i); }
 
 }  // namespace
 
-// One launch over the whole batch (P.n > 0, at most 2^31 - 1 waves: the host
-// splits larger batches).  A variant without a row is an error, never another
-// kernel.
-hipError_t launch_radiance(const rtamd::KernelVariant& v, hipStream_t st, const SceneView& V, const RadianceParams& P) {
-    const RadianceRow* k = radiance_row(v);
-    if (!k) return hipErrorInvalidDeviceFunction;
-    const size_t waves = (P.n + kQueryThreads - 1) / kQueryThreads;
-    if (!P.n || waves > 0x7fffffffu) return hipErrorInvalidValue;
-    const DevScene S = make_scene(V);
-    rtamd::note_launch(kNsName, k->name);
-    hipLaunchKernelGGL(k->fn, dim3((unsigned)waves), dim3(kQueryThreads), kRadiancePool, st, S, P);
-    return hipGetLastError();
-}
-
-rtamd::KernelEntry radiance_kernel(const rtamd::KernelVariant& v) {
-    const RadianceRow* k = radiance_row(v);
-    return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
-}
-
-// Row i of the radiance table as written above (nullptr past the end)
-const char* radiance_row_name(int i) {
-    constexpr int n = (int)(sizeof(kRadianceKernels) / sizeof(kRadianceKernels[0]));
-    return i >= 0 && i < n ? kRadianceKernels[i].name : nullptr;
+const rtamd::KernelTable<RadianceParams>& radiance_table() {
+    static const rtamd::KernelTable<RadianceParams> t = {launch_radiance, radiance_kernel, radiance_row_name,
+                                                         kQueryThreads, kRadiancePool};
+    return t;
 }
 
 }  // namespace RT_NS

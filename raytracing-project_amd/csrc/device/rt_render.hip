@@ -13,9 +13,11 @@
 // (csrc/host/frame_plan.hpp: pick_variant, plan_std_frame, plan_paper_frame,
 // PaperCalls); rt_frame_begin / trace / end here execute that plan.  The
 // rt_test_* hooks live in rt_test_hooks.hip.
+// The batched entry points run on the frames' workspace through one driver
+// (BatchCall: lock, drain, staging arena, counters, chunk loop):
 // Ray queries (rt_query_intersect / rt_query_occluded, Scene::intersect /
-// Scene::occluded for caller-given rays, scene.cpp:10-42): query_impl here,
-// on the frames' workspace and resident scene; kernels in rt_query_kernels.hpp.
+// Scene::occluded for caller-given rays, scene.cpp:10-42): query_impl, on the
+// resident scene; kernels in rt_query_kernels.hpp.
 // Radiance queries (rt_query_radiance, Tracer::trace for caller-given rays,
 // tracer.cpp:12-73): the same query_impl, with the frames' ray counters;
 // kernels in rt_radiance_kernels.hpp.
@@ -24,7 +26,7 @@
 // Camera rays and sample resolve (rt_camera_rays / rt_resolve_samples_device,
 // camera.h:44-78 and tracer.cpp:291-296): camera_rays_impl, on the frames'
 // jitter draws (jitter_plan_ready / jitter_draws, shared with frame_begin);
-// kernels in rt_camera_f64.hip.
+// kernels in rt_camera_f64.hip.  Paper resolve: rt_paper_resolve_device.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -754,7 +756,7 @@ int frame_trace(rt_frame* f, int ri0, int ri1, double* fb, hipStream_t hs, uint8
         HIP_TRY(hipEventRecord(ws.pev[call], st));
         for (int w : c.wait) HIP_TRY(hipStreamWaitEvent(st, ws.pev[w], 0));
         dim3 g2((W + 63) / 64, (n + 3) / 4);
-        HIP_TRY(rtamd::launch_paper_finish(f->kv, g2, st, P));
+        HIP_TRY(rtamd::launch_paper_finish(f->kv, g2, st, f->S, P));
     }
     {
         std::lock_guard<std::mutex> lk(g_setup.mu);
@@ -881,98 +883,180 @@ int render_rows_impl(const rt_scene* s, int W, int H, int mode, int flags, const
     return rc != RT_OK ? rc : rc2;
 }
 
-// ------------------------------------------------------------- ray queries
-// Rays of one launch: 2^30 (the grid's x extent holds 2^31 - 1 one-wave
-// workgroups); rays of one chunk of a query from host memory: 2^20, i.e.
-// 64 MiB of rays + 64 MiB of hits + 1 MiB of flags in the workspace, large
-// enough that a chunk's launch and copy overheads vanish in its transfers.
-constexpr size_t kQueryLaunchRays = (size_t)1 << 30;
-constexpr size_t kQueryChunkRays = (size_t)1 << 20;
+// ------------------------------------------------------ batched-call driver
+// What every batched entry point (the ray, radiance and shading queries, the
+// camera rays, the paper resolve) shares.  An entry point is its argument
+// checks, a BatchCall, its buffers and parameter block, and one run() whose
+// callbacks stage a chunk in, launch, and stage it out.
+//
+// Items (rays, hits, list rows) of one launch: 2^30 (the grid's x extent holds
+// 2^31 - 1 one-wave workgroups).  Items of one chunk of a call from host
+// memory: g_chunk_items, 2^20 unless rt_test_camera_chunk_rays sets another
+// size - for rays 64 MiB of rays + 64 MiB of hits + 1 MiB of flags in the
+// workspace, large enough that a chunk's launch and copy overheads vanish in
+// its transfers.  (The camera rays count it in rays and take whole rows.)
+constexpr size_t kLaunchItems = (size_t)1 << 30;
+constexpr size_t kChunkItems = (size_t)1 << 20;
+std::atomic<size_t> g_chunk_items{kChunkItems};
+constexpr int kKnownFlags = RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH;
 
-// rt_query_{intersect,occluded,radiance}[_device]: kind rtamd::kQueryIsect /
-// kQueryOccl / kQueryRadiance (results: hits and mask / mask / rgb, three
-// doubles per ray).  host: rays and results are host memory, moved through the
-// workspace's chunk buffers; else device memory, traced in place on st.  Holds
-// the workspace lock like a frame, and returns with st drained.  A radiance
-// query counts its Scene::intersect / Scene::occluded calls in the frames'
-// counter slots: zeroed before its first launch, reduced after its last.
-int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays, size_t n, int flags, rt_hit* hits,
-               uint8_t* mask, double* rgb, bool host, hipStream_t st, rt_stats* stats) {
-    const auto t_start = SClock::now();
-    const auto fail = [what](const char* msg, int rc) {
+// One batched call on stream st.  Made first (it takes the call's start time);
+// zero_stats() once the arguments that are checked before the stats are fine;
+// open() before the first use of the device.  From open() on the call holds
+// the workspace lock like a frame, and whatever happens nothing of it is left
+// queued on st when the lock goes (the next frame resets the staging arena the
+// uploads read, and reuses the chunk buffers): the destructor drains st, and
+// runs before the members - the lock - are destroyed.
+struct BatchCall {
+    const char* what;
+    hipStream_t st;
+    rt_stats* stats = nullptr;
+    const SClock::time_point t_start = SClock::now();
+    Workspace* ws = nullptr;
+    std::unique_lock<std::mutex> lock;
+    bool counting = false;     // counters(): finish() reduces the slots
+    double ms_kernel = 0.0;    // run(): the chunks' launches, by the workspace's events
+
+    BatchCall(const char* what_, hipStream_t st_) : what(what_), st(st_) {}
+    BatchCall(const BatchCall&) = delete;
+    ~BatchCall() {
+        if (ws) (void)hipStreamSynchronize(st);
+    }
+    int fail(const char* msg, int rc) const {
         rtamd::set_last_error(std::string(what) + ": " + msg);
         return rc;
-    };
-    const bool isect = kind == rtamd::kQueryIsect, radiance = kind == rtamd::kQueryRadiance;
-    if (!s) return fail("scene is NULL", RT_ERR_INVALID_ARG);
-    if (flags & ~(RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH))
-        return fail("unknown flag bits", RT_ERR_INVALID_ARG);
-    {
-        const int rv = rtamd::check_query_flags(flags);
-        if (rv != RT_OK) return rv;
     }
-    if (stats) {
+    void zero_stats(rt_stats* stats_) {
+        stats = stats_;
+        if (!stats) return;
         std::memset(stats, 0, sizeof(*stats));
         stats->n_gpus = 1;
     }
+    // the device, its workspace and lock, the staging arena reset (the previous
+    // frame's or call's uploads completed), the workspace's events
+    int open() {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        ws = &workspace(dev);
+        lock = std::unique_lock<std::mutex>(ws->mu);   // (waits for an open frame of this device)
+        ws->up.reset();
+        if (!ws->ev[0]) {
+            rtamd::SetupTimer tm(rtamd::kSetupStreams);
+            for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws->ev[i]));
+        }
+        return RT_OK;
+    }
+    // s resident in the workspace, the variant `pick` chooses for it, and its
+    // view with the flat object list (a batch's items are arbitrary)
+    int scene(const rt_scene* s, int flags,
+              int (*pick)(const rtamd::CompiledScene&, const rt_scene_desc&, int, rtamd::KernelVariant*),
+              rtamd::KernelVariant& kv, SceneView& S) {
+        const rt_scene_desc& d = *rt_scene_get_desc(s);
+        int rv = scene_resident(*ws, s, d, false, st);
+        if (rv == RT_OK) rv = pick(ws->sc.cs, d, flags, &kv);
+        if (rv != RT_OK) return rv;
+        scene_view(*ws, d, flags, false, S);
+        S.n_chunks = 0;
+        return RT_OK;
+    }
+    // the frames' ray counter slots, zero before the first launch
+    int counters() {
+        int rv = counters_ready(*ws, st);
+        if (rv == RT_OK) rv = ensure_ctr_host(*ws, kCounterWords);
+        counting = rv == RT_OK;
+        return rv;
+    }
+    // n items in chunks of at most `chunk`, each chunk in launches of at most
+    // launch_max: in(c0, cn) stages items [c0, c0 + cn) in, launch(c0, l0, ln)
+    // launches the chunk's items [l0, l0 + ln), out(c0, cn) stages the results
+    // out; each returns RT_OK or the error to end with.  A chunk is complete
+    // when the next begins (the chunk buffers and the events are reused).  A
+    // call on device memory is one chunk of n with nothing to stage.
+    template <class In, class Launch, class Out>
+    int run(size_t n, size_t chunk, size_t launch_max, In&& in, Launch&& launch, Out&& out) {
+        for (size_t c0 = 0; c0 < n; c0 += chunk) {
+            const size_t cn = std::min(chunk, n - c0);
+            int rv = in(c0, cn);
+            if (rv != RT_OK) return rv;
+            HIP_TRY(hipEventRecord(ws->ev[1], st));
+            for (size_t l0 = 0; l0 < cn && rv == RT_OK; l0 += launch_max) rv = launch(c0, l0, std::min(launch_max, cn - l0));
+            if (rv != RT_OK) return rv;
+            HIP_TRY(hipEventRecord(ws->ev[2], st));
+            rv = out(c0, cn);
+            if (rv != RT_OK) return rv;
+            HIP_TRY(hipStreamSynchronize(st));
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ws->ev[1], ws->ev[2]) == hipSuccess) ms_kernel += ms;
+        }
+        return RT_OK;
+    }
+    static int no_staging(size_t, size_t) { return RT_OK; }
+    // The call's good end: a counting call's slots summed as a frame's end reads
+    // them (ctr(0), ctr(1): the Scene::intersect / Scene::occluded calls; the
+    // slots are left zero), and the times.
+    int finish() {
+        if (counting) {
+            hipLaunchKernelGGL(k_reduce_counters, dim3(kCounterWords), dim3(64), 0, st,
+                               ws->counters.as<unsigned long long>(), ws->ctr_host, nullptr, 0);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(st));
+            ws->counters_zero = true;
+        }
+        if (stats) {
+            stats->ms_kernel = ms_kernel;
+            stats->ms_total = ms_since(t_start);
+        }
+        return RT_OK;
+    }
+    uint64_t ctr(int word) const { return ((volatile unsigned long long*)ws->ctr_host)[word]; }
+};
+
+// ------------------------------------------------------------- ray queries
+// rt_query_{intersect,occluded,radiance}[_device]: kind rtamd::kQueryIsect /
+// kQueryOccl / kQueryRadiance (results: hits and mask / mask / rgb, three
+// doubles per ray).  host: rays and results are host memory, moved through the
+// workspace's chunk buffers; else device memory, traced in place on st.  A
+// radiance query counts its Scene::intersect / Scene::occluded calls.
+int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays, size_t n, int flags, rt_hit* hits,
+               uint8_t* mask, double* rgb, bool host, hipStream_t st, rt_stats* stats) {
+    BatchCall call(what, st);
+    const bool isect = kind == rtamd::kQueryIsect, radiance = kind == rtamd::kQueryRadiance;
+    if (!s) return call.fail("scene is NULL", RT_ERR_INVALID_ARG);
+    if (flags & ~kKnownFlags) return call.fail("unknown flag bits", RT_ERR_INVALID_ARG);
+    int rv = rtamd::check_query_flags(flags);
+    if (rv != RT_OK) return rv;
+    call.zero_stats(stats);
     if (n == 0) return RT_OK;
-    if (!rays) return fail("rays is NULL", RT_ERR_INVALID_ARG);
-    if (radiance ? !rgb : isect ? !hits : !mask) return fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
-    const rt_scene_desc& d = *rt_scene_get_desc(s);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    Workspace& ws = workspace(dev);
-    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
-    // whatever happens below, nothing of this call is left queued on st when
-    // the lock goes (the next frame resets the staging arena the scene upload
-    // reads, and reuses the chunk buffers); declared after the lock: runs first
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{st};
-    ws.up.reset();   // (the previous frame's or query's uploads completed)
-    {
-        const int rv = scene_resident(ws, s, d, false, st);
-        if (rv != RT_OK) return rv;
-    }
+    if (!rays) return call.fail("rays is NULL", RT_ERR_INVALID_ARG);
+    if (radiance ? !rgb : isect ? !hits : !mask) return call.fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
     rtamd::KernelVariant kv;
-    {
-        const int rv = radiance ? rtamd::pick_radiance_variant(ws.sc.cs, d, flags, &kv)
-                                : rtamd::pick_query_variant(ws.sc.cs, d, flags, &kv);
-        if (rv != RT_OK) return rv;
-    }
     SceneView S;
-    scene_view(ws, d, flags, false, S);
-    S.n_chunks = 0;   // (the flat object list)
-    if (!ws.ev[0]) {
-        rtamd::SetupTimer tm(rtamd::kSetupStreams);
-        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
-    }
-    if (radiance) {
-        int rv = counters_ready(ws, st);
-        if (rv == RT_OK) rv = ensure_ctr_host(ws, kCounterWords);
-        if (rv != RT_OK) return rv;
-    }
-    const size_t chunk = host ? std::min(n, kQueryChunkRays) : n;
+    rv = call.open();
+    if (rv == RT_OK) rv = call.scene(s, flags, radiance ? rtamd::pick_radiance_variant : rtamd::pick_query_variant, kv, S);
+    if (rv == RT_OK && radiance) rv = call.counters();
+    if (rv != RT_OK) return rv;
+    Workspace& ws = *call.ws;
+    const size_t chunk = host ? std::min(n, g_chunk_items.load()) : n;
     if (host) {
         HIP_TRY(ws.q_rays.ensure(chunk * sizeof(rt_ray)));
         if (isect) HIP_TRY(ws.q_hits.ensure(chunk * sizeof(rt_hit)));
         if (mask) HIP_TRY(ws.q_mask.ensure(chunk));
         if (radiance) HIP_TRY(ws.q_rgb.ensure(chunk * 3 * sizeof(double)));
     }
-    double ms_kernel = 0.0;
-    for (size_t c0 = 0; c0 < n; c0 += chunk) {
-        const size_t cn = std::min(chunk, n - c0);
-        const rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays + c0;
-        rt_hit* d_hits = !isect ? nullptr : host ? ws.q_hits.as<rt_hit>() : hits + c0;
-        uint8_t* d_mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask + c0;
-        double* d_rgb = !radiance ? nullptr : host ? ws.q_rgb.as<double>() : rgb + 3 * c0;
-        if (host) HIP_TRY(hipMemcpyAsync(ws.q_rays.p, rays + c0, cn * sizeof(rt_ray), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(ws.ev[1], st));
-        for (size_t l0 = 0; l0 < cn; l0 += kQueryLaunchRays) {
-            const size_t ln = std::min(kQueryLaunchRays, cn - l0);
+    // a chunk on the device: the staging buffers, or the caller's (one chunk)
+    const rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays;
+    rt_hit* d_hits = !isect ? nullptr : host ? ws.q_hits.as<rt_hit>() : hits;
+    uint8_t* d_mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask;
+    double* d_rgb = !radiance ? nullptr : host ? ws.q_rgb.as<double>() : rgb;
+    rv = call.run(
+        n, chunk, kLaunchItems,
+        [&](size_t c0, size_t cn) -> int {
+            if (host) HIP_TRY(hipMemcpyAsync(ws.q_rays.p, rays + c0, cn * sizeof(rt_ray), hipMemcpyHostToDevice, st));
+            return RT_OK;
+        },
+        [&](size_t, size_t l0, size_t ln) -> int {
             if (radiance) {
                 RadianceParams P;
                 P.n = ln;
@@ -988,36 +1072,20 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
                 P.mask = d_mask ? d_mask + l0 : nullptr;
                 HIP_TRY(rtamd::launch_query(kv, kind, st, S, P));
             }
-        }
-        HIP_TRY(hipEventRecord(ws.ev[2], st));
-        if (host) {
+            return RT_OK;
+        },
+        [&](size_t c0, size_t cn) -> int {
+            if (!host) return RT_OK;
             if (isect) HIP_TRY(hipMemcpyAsync(hits + c0, d_hits, cn * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
             if (mask) HIP_TRY(hipMemcpyAsync(mask + c0, d_mask, cn, hipMemcpyDeviceToHost, st));
             if (radiance) HIP_TRY(hipMemcpyAsync(rgb + 3 * c0, d_rgb, cn * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        // (the chunk buffers and the events are reused by the next chunk)
-        HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) ms_kernel += ms;
-    }
-    uint64_t n_isect = isect ? n : 0, n_occl = radiance || isect ? 0 : n;
-    if (radiance) {
-        // the slots' sums, as a frame's end reads them (and the slots are left zero)
-        hipLaunchKernelGGL(k_reduce_counters, dim3(kCounterWords), dim3(64), 0, st, ws.counters.as<unsigned long long>(),
-                           ws.ctr_host, nullptr, 0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        ws.counters_zero = true;
-        n_isect = ((volatile unsigned long long*)ws.ctr_host)[0];
-        n_occl = ((volatile unsigned long long*)ws.ctr_host)[1];
-    }
-    if (stats) {
-        stats->rays_intersect = n_isect;
-        stats->rays_occluded = n_occl;
-        stats->rays_traced = n_isect + n_occl;
-        stats->ms_kernel = ms_kernel;
-        stats->ms_total = ms_since(t_start);
-    }
+            return RT_OK;
+        });
+    if (rv == RT_OK) rv = call.finish();
+    if (rv != RT_OK || !stats) return rv;
+    stats->rays_intersect = radiance ? call.ctr(0) : isect ? n : 0;
+    stats->rays_occluded = radiance ? call.ctr(1) : isect ? 0 : n;
+    stats->rays_traced = stats->rays_intersect + stats->rays_occluded;
     return RT_OK;
 }
 
@@ -1027,58 +1095,27 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
 // host memory in both forms.  n_lights >= 0: the call's own point lights, in a
 // workspace buffer of their own (uploaded through the page-locked arena);
 // only this call's SceneView points there, so the resident scene (ws.lights,
-// the scene cache) is what it was.  Holds the workspace lock like a frame,
-// and returns with st drained.  The Scene::occluded calls are counted in the
-// frames' counter slots: zeroed before the first launch, reduced after the last.
+// the scene cache) is what it was.  The Scene::occluded calls are counted.
 int shade_impl(const char* what, const rt_scene* s, const rt_hit* hits, const double* wo, const uint8_t* mask, size_t n,
                const rt_light* lights, int n_lights, const double* miss_rgb, int flags, double* rgb, bool host,
                hipStream_t st, rt_stats* stats) {
-    const auto t_start = SClock::now();
-    const auto fail = [what](const char* msg, int rc) {
-        rtamd::set_last_error(std::string(what) + ": " + msg);
-        return rc;
-    };
-    if (!s) return fail("scene is NULL", RT_ERR_INVALID_ARG);
-    if (flags & ~(RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH))
-        return fail("unknown flag bits", RT_ERR_INVALID_ARG);
-    {
-        const int rv = rtamd::check_query_flags(flags);
-        if (rv != RT_OK) return rv;
-    }
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_gpus = 1;
-    }
+    BatchCall call(what, st);
+    if (!s) return call.fail("scene is NULL", RT_ERR_INVALID_ARG);
+    if (flags & ~kKnownFlags) return call.fail("unknown flag bits", RT_ERR_INVALID_ARG);
+    int rv = rtamd::check_query_flags(flags);
+    if (rv != RT_OK) return rv;
+    call.zero_stats(stats);
     if (n == 0) return RT_OK;
-    if (!hits) return fail("hits is NULL", RT_ERR_INVALID_ARG);
-    if (!wo) return fail("wo is NULL", RT_ERR_INVALID_ARG);
-    if (!rgb) return fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
-    if (n_lights > 0 && !lights) return fail("lights is NULL with n_lights > 0", RT_ERR_INVALID_ARG);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
-    const rt_scene_desc& d = *rt_scene_get_desc(s);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    Workspace& ws = workspace(dev);
-    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
-    // (as query_impl: nothing of this call stays queued on st when the lock goes)
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{st};
-    ws.up.reset();   // (the previous frame's or query's uploads completed)
-    {
-        const int rv = scene_resident(ws, s, d, false, st);
-        if (rv != RT_OK) return rv;
-    }
+    if (!hits) return call.fail("hits is NULL", RT_ERR_INVALID_ARG);
+    if (!wo) return call.fail("wo is NULL", RT_ERR_INVALID_ARG);
+    if (!rgb) return call.fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
+    if (n_lights > 0 && !lights) return call.fail("lights is NULL with n_lights > 0", RT_ERR_INVALID_ARG);
     rtamd::KernelVariant kv;
-    {
-        const int rv = rtamd::pick_shade_variant(ws.sc.cs, d, flags, &kv);
-        if (rv != RT_OK) return rv;
-    }
     SceneView S;
-    scene_view(ws, d, flags, false, S);
-    S.n_chunks = 0;   // (the flat object list)
+    rv = call.open();
+    if (rv == RT_OK) rv = call.scene(s, flags, rtamd::pick_shade_variant, kv, S);
+    if (rv != RT_OK) return rv;
+    Workspace& ws = *call.ws;
     if (n_lights >= 0) {
         // this call's point lights: k_shade (WV = 0) reads nothing else by light number
         HIP_TRY(ws.q_lights.ensure(n_lights ? (size_t)n_lights * sizeof(rt_light) : 16));
@@ -1086,95 +1123,70 @@ int shade_impl(const char* what, const rt_scene* s, const rt_hit* hits, const do
         S.lights = ws.q_lights.p;
         S.n_lights = n_lights;
     }
-    if (!ws.ev[0]) {
-        rtamd::SetupTimer tm(rtamd::kSetupStreams);
-        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
-    }
-    {
-        int rv = counters_ready(ws, st);
-        if (rv == RT_OK) rv = ensure_ctr_host(ws, kCounterWords);
-        if (rv != RT_OK) return rv;
-    }
-    const size_t chunk = host ? std::min(n, kQueryChunkRays) : n;
+    rv = call.counters();
+    if (rv != RT_OK) return rv;
+    const size_t chunk = host ? std::min(n, g_chunk_items.load()) : n;
     if (host) {
         HIP_TRY(ws.q_hits.ensure(chunk * sizeof(rt_hit)));
         HIP_TRY(ws.q_wo.ensure(chunk * 3 * sizeof(double)));
         if (mask) HIP_TRY(ws.q_mask.ensure(chunk));
         HIP_TRY(ws.q_rgb.ensure(chunk * 3 * sizeof(double)));
     }
-    double ms_kernel = 0.0;
-    for (size_t c0 = 0; c0 < n; c0 += chunk) {
-        const size_t cn = std::min(chunk, n - c0);
-        const rt_hit* d_hits = host ? ws.q_hits.as<rt_hit>() : hits + c0;
-        const double* d_wo = host ? ws.q_wo.as<double>() : wo + 3 * c0;
-        const uint8_t* d_mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask + c0;
-        double* d_rgb = host ? ws.q_rgb.as<double>() : rgb + 3 * c0;
-        if (host) {
+    // a chunk on the device: the staging buffers, or the caller's (one chunk)
+    ShadeParams P0;
+    P0.hits = host ? ws.q_hits.as<rt_hit>() : hits;
+    P0.wo = host ? ws.q_wo.as<double>() : wo;
+    P0.mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask;
+    P0.rgb = host ? ws.q_rgb.as<double>() : rgb;
+    for (int c = 0; c < 3; ++c) P0.miss[c] = miss_rgb ? miss_rgb[c] : rt_scene_get_desc(s)->background[c];
+    P0.counters = ws.counters.as<unsigned long long>();
+    rv = call.run(
+        n, chunk, kLaunchItems,
+        [&](size_t c0, size_t cn) -> int {
+            if (!host) return RT_OK;
             HIP_TRY(hipMemcpyAsync(ws.q_hits.p, hits + c0, cn * sizeof(rt_hit), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(ws.q_wo.p, wo + 3 * c0, cn * 3 * sizeof(double), hipMemcpyHostToDevice, st));
             if (mask) HIP_TRY(hipMemcpyAsync(ws.q_mask.p, mask + c0, cn, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipEventRecord(ws.ev[1], st));
-        for (size_t l0 = 0; l0 < cn; l0 += kQueryLaunchRays) {
-            ShadeParams P;
-            P.n = std::min(kQueryLaunchRays, cn - l0);
-            P.hits = d_hits + l0;
-            P.wo = d_wo + 3 * l0;
-            P.mask = d_mask ? d_mask + l0 : nullptr;
-            P.rgb = d_rgb + 3 * l0;
-            for (int c = 0; c < 3; ++c) P.miss[c] = miss_rgb ? miss_rgb[c] : d.background[c];
-            P.counters = ws.counters.as<unsigned long long>();
+            return RT_OK;
+        },
+        [&](size_t, size_t l0, size_t ln) -> int {
+            ShadeParams P = P0;
+            P.n = ln;
+            P.hits += l0;
+            P.wo += 3 * l0;
+            if (P.mask) P.mask += l0;
+            P.rgb += 3 * l0;
             HIP_TRY(rtamd::launch_shade(kv, st, S, P));
-        }
-        HIP_TRY(hipEventRecord(ws.ev[2], st));
-        if (host) HIP_TRY(hipMemcpyAsync(rgb + 3 * c0, d_rgb, cn * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        // (the chunk buffers and the events are reused by the next chunk)
-        HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) ms_kernel += ms;
-    }
-    // the slots' sums, as a frame's end reads them (and the slots are left zero)
-    hipLaunchKernelGGL(k_reduce_counters, dim3(kCounterWords), dim3(64), 0, st, ws.counters.as<unsigned long long>(),
-                       ws.ctr_host, nullptr, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    ws.counters_zero = true;
-    if (stats) {
-        stats->rays_occluded = ((volatile unsigned long long*)ws.ctr_host)[1];
-        stats->rays_traced = stats->rays_occluded;
-        stats->ms_kernel = ms_kernel;
-        stats->ms_total = ms_since(t_start);
-    }
+            return RT_OK;
+        },
+        [&](size_t c0, size_t cn) -> int {
+            if (host) HIP_TRY(hipMemcpyAsync(rgb + 3 * c0, P0.rgb, cn * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            return RT_OK;
+        });
+    if (rv == RT_OK) rv = call.finish();
+    if (rv != RT_OK || !stats) return rv;
+    stats->rays_occluded = call.ctr(1);
+    stats->rays_traced = stats->rays_occluded;
     return RT_OK;
 }
 
 // ------------------------------------------------------------- camera rays
-// Rays of one chunk of rt_camera_rays (the host form): the queries' chunk, so
-// the same staging buffer (q_rays) serves; rt_test_camera_chunk_rays sets
-// another size (0: back to this one).
-std::atomic<size_t> g_camera_chunk_rays{kQueryChunkRays};
-
 // rt_camera_rays[_device]: the rays of list entries [0, n_rows) of a W x H
 // frame seen through cam (k_camera_rays, rt_camera_f64.hip).  host: rays is
-// host memory, filled through the workspace's ray staging buffer in row chunks
-// of at most g_camera_chunk_rays rays (at least one row); else device memory,
-// written in place on st.  Jittered rays read the frames' draws (jitter_plan_ready
-// / jitter_draws: the frames' plan, checkpoint table, cache key and fill), one
-// acquisition for the whole list whatever the chunks.  Holds the workspace
-// lock like a frame, and returns with st drained.
+// host memory, filled through the workspace's ray staging buffer (q_rays, the
+// queries') in row chunks of at most g_chunk_items rays (at least one row);
+// else device memory, written in place on st.  Jittered rays read the frames'
+// draws (jitter_plan_ready / jitter_draws: the frames' plan, checkpoint table,
+// cache key and fill), one acquisition for the whole list whatever the chunks.
 int camera_rays_impl(const char* what, const rt_camera* cam, int W, int H, int kind, const int32_t* rows_host, int n_rows,
                      rt_ray* rays, bool host, hipStream_t st, rt_stats* stats) {
-    const auto t_start = SClock::now();
-    const auto fail = [what](const char* msg, int rc) {
-        rtamd::set_last_error(std::string(what) + ": " + msg);
-        return rc;
-    };
-    if (!cam) return fail("cam is NULL", RT_ERR_INVALID_ARG);
-    if (W <= 0 || H <= 0) return fail("W and H must be > 0", RT_ERR_INVALID_ARG);
-    if (kind != RT_RAYS_CENTRE && kind != RT_RAYS_JITTERED) return fail("unknown kind", RT_ERR_INVALID_ARG);
-    if ((size_t)W * RT_SPP >= ((size_t)1 << 31)) return fail("W is beyond one launch's row", RT_ERR_INVALID_ARG);
-    if (n_rows < 0 || n_rows > H) return fail("bad rows", RT_ERR_INVALID_ARG);
-    if (!rows_host && n_rows != 0 && n_rows != H) return fail("rows is NULL with n_rows != H", RT_ERR_INVALID_ARG);
+    BatchCall call(what, st);
+    if (!cam) return call.fail("cam is NULL", RT_ERR_INVALID_ARG);
+    if (W <= 0 || H <= 0) return call.fail("W and H must be > 0", RT_ERR_INVALID_ARG);
+    if (kind != RT_RAYS_CENTRE && kind != RT_RAYS_JITTERED) return call.fail("unknown kind", RT_ERR_INVALID_ARG);
+    if ((size_t)W * RT_SPP >= ((size_t)1 << 31)) return call.fail("W is beyond one launch's row", RT_ERR_INVALID_ARG);
+    if (n_rows < 0 || n_rows > H) return call.fail("bad rows", RT_ERR_INVALID_ARG);
+    if (!rows_host && n_rows != 0 && n_rows != H) return call.fail("rows is NULL with n_rows != H", RT_ERR_INVALID_ARG);
     const bool jittered = kind == RT_RAYS_JITTERED;
     std::vector<int32_t> all_rows;
     bool in_order = true;   // entry ri is row ri
@@ -1185,33 +1197,17 @@ int camera_rays_impl(const char* what, const rt_camera* cam, int W, int H, int k
     } else {
         std::vector<char> seen(H, 0);
         for (int i = 0; i < n_rows; ++i) {
-            if (rows_host[i] < 0 || rows_host[i] >= H) return fail("row out of range", RT_ERR_INVALID_ARG);
-            if (seen[rows_host[i]]++) return fail("duplicate row", RT_ERR_INVALID_ARG);
+            if (rows_host[i] < 0 || rows_host[i] >= H) return call.fail("row out of range", RT_ERR_INVALID_ARG);
+            if (seen[rows_host[i]]++) return call.fail("duplicate row", RT_ERR_INVALID_ARG);
             in_order = in_order && rows_host[i] == i;
         }
     }
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_gpus = 1;
-    }
+    call.zero_stats(stats);
     if (n_rows == 0) return RT_OK;
-    if (!rays) return fail("the ray buffer is NULL", RT_ERR_INVALID_ARG);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available", RT_ERR_NO_DEVICE);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    Workspace& ws = workspace(dev);
-    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
-    // (as query_impl: nothing of this call stays queued on st when the lock goes)
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{st};
-    ws.up.reset();   // (the previous frame's or query's uploads completed)
-    if (!ws.ev[0]) {
-        rtamd::SetupTimer tm(rtamd::kSetupStreams);
-        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
-    }
+    if (!rays) return call.fail("the ray buffer is NULL", RT_ERR_INVALID_ARG);
+    int rv = call.open();
+    if (rv != RT_OK) return rv;
+    Workspace& ws = *call.ws;
     rtamd::CameraParams P{};
     for (int i = 0; i < 3; ++i) {
         P.eye[i] = cam->eye[i];
@@ -1227,16 +1223,12 @@ int camera_rays_impl(const char* what, const rt_camera* cam, int W, int H, int k
     float ms_rng = 0.f;
     if (jittered) {
         rtamd::StdPlan plan;   // (host source of the rows upload: alive until st is drained)
-        {
-            const int rv = jitter_plan_ready(ws, W, H, rows_host, n_rows, st, plan);
-            if (rv != RT_OK) return rv;
-        }
+        rv = jitter_plan_ready(ws, W, H, rows_host, n_rows, st, plan);
+        if (rv != RT_OK) return rv;
         HIP_TRY(hipEventRecord(ws.ev[0], st));
         bool filled = false;
-        {
-            const int rv = jitter_draws(ws, what, W, H, n_rows, plan, st, &jent, &filled);
-            if (rv != RT_OK) return rv;
-        }
+        rv = jitter_draws(ws, what, W, H, n_rows, plan, st, &jent, &filled);
+        if (rv != RT_OK) return rv;
         HIP_TRY(hipEventRecord(ws.ev[1], st));
         // (the plan's vectors must outlive the upload: wait here, once per call)
         HIP_TRY(hipStreamSynchronize(st));
@@ -1252,46 +1244,38 @@ int camera_rays_impl(const char* what, const rt_camera* cam, int W, int H, int k
     }
     const size_t per_row = (size_t)W * (jittered ? RT_SPP : 1);
     // list entries of one launch: the grid's y extent; of one host chunk: its rays
-    const int launch_rows = 65535;
-    const int chunk_rows =
-        host ? (int)std::min<size_t>((size_t)n_rows, std::max<size_t>(1, g_camera_chunk_rays.load() / per_row)) : n_rows;
-    if (host) HIP_TRY(ws.q_rays.ensure((size_t)chunk_rows * per_row * sizeof(rt_ray)));
-    double ms_kernel = 0.0;
-    for (int c0 = 0; c0 < n_rows; c0 += chunk_rows) {
-        const int cn = std::min(chunk_rows, n_rows - c0);
-        rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays + (size_t)c0 * per_row;
-        HIP_TRY(hipEventRecord(ws.ev[1], st));
-        for (int l0 = 0; l0 < cn; l0 += launch_rows) {
-            P.ri0 = c0 + l0;
-            P.n_rows = std::min(launch_rows, cn - l0);
-            P.rays = d_rays + (size_t)l0 * per_row;
+    const size_t launch_rows = 65535;
+    const size_t chunk_rows = host ? std::min<size_t>(n_rows, std::max<size_t>(1, g_chunk_items.load() / per_row)) : n_rows;
+    if (host) HIP_TRY(ws.q_rays.ensure(chunk_rows * per_row * sizeof(rt_ray)));
+    rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays;
+    rv = call.run(
+        n_rows, chunk_rows, launch_rows, BatchCall::no_staging,
+        [&](size_t c0, size_t l0, size_t ln) -> int {
+            P.ri0 = (int)(c0 + l0);
+            P.n_rows = (int)ln;
+            P.rays = d_rays + l0 * per_row;
             HIP_TRY(rtd::launch_camera_rays(jittered, st, P));
-        }
-        HIP_TRY(hipEventRecord(ws.ev[2], st));
-        if (host)
-            HIP_TRY(hipMemcpyAsync(rays + (size_t)c0 * per_row, d_rays, (size_t)cn * per_row * sizeof(rt_ray),
-                                   hipMemcpyDeviceToHost, st));
-        // (the chunk buffer and the events are reused by the next chunk)
-        HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) ms_kernel += ms;
-    }
+            return RT_OK;
+        },
+        [&](size_t c0, size_t cn) -> int {
+            if (host) HIP_TRY(hipMemcpyAsync(rays + c0 * per_row, d_rays, cn * per_row * sizeof(rt_ray), hipMemcpyDeviceToHost, st));
+            return RT_OK;
+        });
+    if (rv != RT_OK) return rv;
     // st has run to its end: the draws and the rows list this call wrote are
     // complete, and later frames or calls of its key may read them
     ws.jcache.complete(jent);
-    if (stats) {
-        stats->pixels = (uint64_t)n_rows * W;
-        stats->ms_rng = ms_rng;
-        stats->ms_kernel = ms_kernel;
-        stats->ms_total = ms_since(t_start);
-    }
+    rv = call.finish();
+    if (rv != RT_OK || !stats) return rv;
+    stats->pixels = (uint64_t)n_rows * W;
+    stats->ms_rng = ms_rng;
     return RT_OK;
 }
 
 }  // namespace
 
 extern "C" int rt_test_camera_chunk_rays(size_t n) {
-    g_camera_chunk_rays.store(n ? n : kQueryChunkRays);
+    g_chunk_items.store(n ? n : kChunkItems);
     return RT_OK;
 }
 
@@ -1343,7 +1327,7 @@ extern "C" int rt_warmup(int what) {
         hipFuncAttributes a{};
         rtamd::KernelVariant lean;   // (k_std_lean<false, 1, false>)
         lean.wv = 1;
-        HIP_TRY(hipFuncGetAttributes(&a, rtd::std_kernel(lean).fn));
+        HIP_TRY(hipFuncGetAttributes(&a, rtamd::trace_kernel(lean, false).fn));
     }
     return RT_OK;
 }
@@ -1702,38 +1686,19 @@ extern "C" int rt_rays_wo_device(const rt_ray* rays_dev, size_t n, double* wo_de
 
 // rt_paper_resolve_device: k_paper_resolve (rt_paper_f64.hip) over the
 // caller's device buffers.  No scene: nothing is uploaded and the resident
-// scene copy is not touched.  Holds the workspace lock like a frame (its
-// events time the kernel), and returns with the stream drained.
+// scene copy is not touched.  A batched call (BatchCall: the workspace's
+// events time the kernel) of one chunk and one launch.
 extern "C" int rt_paper_resolve_device(const rt_hit* hits_dev, const uint8_t* hit_mask_dev, const double* rgb_dev, int W,
                                        int H, int row0, int n_rows, double* fb_dev, double* edge_dev, void* hip_stream,
                                        rt_stats* stats) {
-    const auto t_start = SClock::now();
-    const int rc = rtamd::paper_resolve_check("rt_paper_resolve_device", hits_dev, hit_mask_dev, rgb_dev, W, H, row0,
-                                              n_rows, fb_dev, edge_dev);
-    if (rc != RT_OK) return rc;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_gpus = 1;
-    }
-    if (n_rows == 0) return RT_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        rtamd::set_last_error("rt_paper_resolve_device: no HIP device available");
-        return RT_ERR_NO_DEVICE;
-    }
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     const hipStream_t st = (hipStream_t)hip_stream;
-    Workspace& ws = workspace(dev);
-    std::unique_lock<std::mutex> lock(ws.mu);   // (waits for an open frame of this device)
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{st};
-    if (!ws.ev[0]) {
-        rtamd::SetupTimer tm(rtamd::kSetupStreams);
-        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ws.ev[i]));
-    }
+    BatchCall call("rt_paper_resolve_device", st);
+    int rc = rtamd::paper_resolve_check(call.what, hits_dev, hit_mask_dev, rgb_dev, W, H, row0, n_rows, fb_dev, edge_dev);
+    if (rc != RT_OK) return rc;
+    call.zero_stats(stats);
+    if (n_rows == 0) return RT_OK;
+    rc = call.open();
+    if (rc != RT_OK) return rc;
     rtamd::PaperResolveParams P;
     P.hits = hits_dev;
     P.mask = hit_mask_dev;
@@ -1744,17 +1709,16 @@ extern "C" int rt_paper_resolve_device(const rt_hit* hits_dev, const uint8_t* hi
     P.n_rows = n_rows;
     P.fb = fb_dev;
     P.edge = edge_dev;
-    HIP_TRY(hipEventRecord(ws.ev[1], st));
-    HIP_TRY(rtd::launch_paper_resolve(st, P));
-    HIP_TRY(hipEventRecord(ws.ev[2], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (stats) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ws.ev[1], ws.ev[2]) == hipSuccess) stats->ms_kernel = ms;
-        stats->pixels = (uint64_t)n_rows * W;
-        stats->ms_total = ms_since(t_start);
-    }
-    return RT_OK;
+    rc = call.run(
+        n_rows, n_rows, n_rows, BatchCall::no_staging,
+        [&](size_t, size_t, size_t) -> int {
+            HIP_TRY(rtd::launch_paper_resolve(st, P));
+            return RT_OK;
+        },
+        BatchCall::no_staging);
+    if (rc == RT_OK) rc = call.finish();
+    if (rc == RT_OK && stats) stats->pixels = (uint64_t)n_rows * W;
+    return rc;
 }
 
 extern "C" int rt_scatter_rows_device(const double* src_dev, const int32_t* rows_dev, int n_rows, int W,

@@ -25,6 +25,8 @@
 // scene read; the stores of lanes past the end are masked.  Dynamic LDS:
 // pool_bytes(64), shade()'s light cache (wave_pool).
 
+#include "rt_kernel_table.hpp"
+
 namespace RT_NS {
 
 using rtamd::kCounterSlots;
@@ -34,7 +36,6 @@ using rtamd::ShadeParams;
 
 namespace {
 
-constexpr int kQueryThreads = 64;
 constexpr size_t kShadePool = pool_bytes(kQueryThreads);
 
 // The wave's Scene::occluded call count: reduced by shuffles, then one 64-bit
@@ -93,19 +94,12 @@ __global__ __launch_bounds__(kQueryThreads) void k_shade(DevScene S, ShadeParams
     flush_occl_count(P.counters, valid ? no : 0u);
 }
 
-// The shade kernels by variant, as the query kernels' table (the occluded
-// query's columns): each written once with its template arguments spelled out,
-// so that an entry's name is the instantiation as rocprofv3 prints it.
-// Columns: E D PL.  RT_GENERAL_ONLY (the big-stack build) keeps the general
-// row alone.
+// The shade kernels by variant, in the tables' one form (rt_kernel_table.hpp;
+// the occluded query's columns).  Columns: E D PL.  RT_GENERAL_ONLY (the
+// big-stack build) keeps the general row alone.
 constexpr unsigned skey(bool e, bool d, bool pl) { return (unsigned)e | (unsigned)d << 1 | (unsigned)pl << 2; }
-struct ShadeRow {
-    unsigned key;
-    void (*fn)(DevScene, ShadeParams);
-    const char* name;
-};
-#define RT_SHD(e, d, pl, ...) {skey(e, d, pl), __VA_ARGS__, #__VA_ARGS__}
-const ShadeRow kShadeKernels[] = {
+#define RT_SHD(e, d, pl, ...) RT_KERNEL_ROW(skey(e, d, pl), __VA_ARGS__)
+const KernelRow<DevScene, ShadeParams> kShadeKernels[] = {
     RT_SHD(1, 1, 0, k_shade<true, true, false>),
 #ifndef RT_GENERAL_ONLY
     RT_SHD(0, 1, 0, k_shade<false, true, false>),
@@ -115,39 +109,23 @@ const ShadeRow kShadeKernels[] = {
 };
 #undef RT_SHD
 
-const ShadeRow* shade_row(const rtamd::KernelVariant& v) {
-    const unsigned key = skey(v.eager, v.deep, v.plain);
-    for (const ShadeRow& r : kShadeKernels)
-        if (r.key == key) return &r;
-    return nullptr;
+const KernelRow<DevScene, ShadeParams>* shade_row(const rtamd::KernelVariant& v) {
+    return find_kernel(kShadeKernels, skey(v.eager, v.deep, v.plain));
 }
+
+// (V.lights / V.n_lights are the call's point lights: launch_lanes' own_lights)
+hipError_t launch_shade(const rtamd::KernelVariant& v, int, dim3, hipStream_t st, const SceneView& V,
+                        const ShadeParams& P) {
+    return launch_lanes(shade_row(v), kShadePool, true, st, V, P);
+}
+rtamd::KernelEntry shade_kernel(const rtamd::KernelVariant& v, int) { return kernel_entry(shade_row(v)); }
+const char* shade_row_name(int i) { return row_name(kShadeKernels, i); }
 
 }  // namespace
 
-// One launch over the whole batch (P.n > 0, at most 2^31 - 1 waves: the host
-// splits larger batches).  V.lights / V.n_lights are the call's point lights.
-// A variant without a row is an error, never another kernel.
-hipError_t launch_shade(const rtamd::KernelVariant& v, hipStream_t st, const SceneView& V, const ShadeParams& P) {
-    const ShadeRow* k = shade_row(v);
-    if (!k) return hipErrorInvalidDeviceFunction;
-    const size_t waves = (P.n + kQueryThreads - 1) / kQueryThreads;
-    if (!P.n || waves > 0x7fffffffu) return hipErrorInvalidValue;
-    DevScene S = make_scene(V);
-    S.lrec = S.lgb = nullptr;   // (indexed by the scene's own light numbers: WV kernels only)
-    rtamd::note_launch(kNsName, k->name);
-    hipLaunchKernelGGL(k->fn, dim3((unsigned)waves), dim3(kQueryThreads), kShadePool, st, S, P);
-    return hipGetLastError();
-}
-
-rtamd::KernelEntry shade_kernel(const rtamd::KernelVariant& v) {
-    const ShadeRow* k = shade_row(v);
-    return k ? rtamd::KernelEntry{(const void*)k->fn, k->name} : rtamd::KernelEntry{nullptr, nullptr};
-}
-
-// Row i of the shade table as written above (nullptr past the end)
-const char* shade_row_name(int i) {
-    constexpr int n = (int)(sizeof(kShadeKernels) / sizeof(kShadeKernels[0]));
-    return i >= 0 && i < n ? kShadeKernels[i].name : nullptr;
+const rtamd::KernelTable<ShadeParams>& shade_table() {
+    static const rtamd::KernelTable<ShadeParams> t = {launch_shade, shade_kernel, shade_row_name, kQueryThreads, kShadePool};
+    return t;
 }
 
 }  // namespace RT_NS

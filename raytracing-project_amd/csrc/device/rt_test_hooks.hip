@@ -31,22 +31,61 @@
 namespace {
 using DBuf = rtamd::DevBufT<8>;
 
-// The variant a frame of (s, mode, flags) launches: the frame's own
-// pick_variant, its BVH trial aside.
-int scene_variant(const rt_scene* s, int mode, int flags, rtamd::KernelVariant* v) {
-    if (mode != RT_MODE_STANDARD && mode != RT_MODE_PAPER) return RT_ERR_INVALID_ARG;
+using rtamd::KernelNamespace;
+using rtamd::KernelVariant;
+
+// The variant pick(compiled scene, desc, &v) chooses for scene s
+template <class Pick>
+int scene_variant(const rt_scene* s, Pick pick, KernelVariant* v) {
     try {
         const rt_scene_desc& d = *rt_scene_get_desc(s);
-        return rtamd::pick_variant(rtamd::compile_scene(d), d, mode, flags, true, v);
+        return pick(rtamd::compile_scene(d), d, v);
     } catch (const std::exception& e) {
         rtamd::set_last_error(std::string("scene compile: ") + e.what());
         return RT_ERR_INVALID_ARG;
     }
 }
+// The variant a frame of (mode, flags) launches: the frame's own pick_variant,
+// its BVH trial aside; of a query family: its pick_*_variant (frame_plan.hpp).
+auto frame_pick(int mode, int flags) {
+    return [=](const rtamd::CompiledScene& cs, const rt_scene_desc& d, KernelVariant* v) {
+        return rtamd::pick_variant(cs, d, mode, flags, true, v);
+    };
+}
+auto query_pick(int (*pick)(const rtamd::CompiledScene&, const rt_scene_desc&, int, KernelVariant*), int flags) {
+    return [=](const rtamd::CompiledScene& cs, const rt_scene_desc& d, KernelVariant* v) { return pick(cs, d, flags, v); };
+}
+
+// out <- "ns::name" of the kernel entry(v) of the variant `pick` chooses for s
+// (rt_test_*_kernel_name; `what`: the hook)
+template <class Pick, class Entry>
+int kernel_name(const char* what, const rt_scene* s, char* out, int cap, Pick pick, Entry entry) {
+    if (!s || !out || cap <= 0) return RT_ERR_INVALID_ARG;
+    KernelVariant v;
+    const int rc = scene_variant(s, pick, &v);
+    if (rc != RT_OK) return rc;
+    const rtamd::KernelEntry k = entry(v);
+    if (!k.name) {
+        rtamd::set_last_error(std::string(what) + ": no kernel for this variant");
+        return RT_ERR_UNSUPPORTED;
+    }
+    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
+    return RT_OK;
+}
+
+// out <- row `index` of namespace ns's `table` as "ns::name" (rt_test_*_kernel_row)
+template <class T>
+int kernel_row(int ns, T KernelNamespace::*table, int index, char* out, int cap) {
+    const KernelNamespace& n = rtamd::kernel_namespace(ns);
+    const char* name = out && cap > 0 && index >= 0 && n.*table ? (n.*table)->row_name(index) : nullptr;
+    if (!name) return RT_ERR_INVALID_ARG;
+    std::snprintf(out, (size_t)cap, "%s::%s", n.name, name);
+    return RT_OK;
+}
 }  // namespace
 
 // ------------------------------------------------------------- launch log
-// note_launch is called by every launcher (rt_kernels.hpp, rt_query_kernels.hpp, rt_radiance_kernels.hpp, rt_shade_kernels.hpp)
+// note_launch is called by every launcher (rt_kernels.hpp, rt_kernel_table.hpp launch_lanes)
 // right before its hipLaunchKernelGGL; off, it is one relaxed load.
 namespace {
 std::atomic<int> g_log_on{0};
@@ -85,32 +124,26 @@ extern "C" int rt_test_launch_log_get(char* out, int cap) {
 }
 
 extern "C" int rt_test_kernel_row(int table, int index, char* out, int cap) {
-    if (!out || cap <= 0 || index < 0) return RT_ERR_INVALID_ARG;
-    const char* ns = nullptr;
-    const char* name = nullptr;
+    enum { kRtd = KernelVariant::kRtd, kRtf = KernelVariant::kRtf, kRtdb = KernelVariant::kRtdb };
     switch (table) {
-        case 0: ns = "rtd", name = rtd::std_row_name(index); break;
-        case 1: ns = "rtd", name = rtd::paper_row_name(index); break;
-        case 2: ns = "rtf", name = rtf::std_row_name(index); break;
-        case 3: ns = "rtf", name = rtf::paper_row_name(index); break;
-        case 4: ns = "rtdb", name = rtdb::std_row_name(index); break;
-        case 5: ns = "rtdb", name = rtdb::paper_row_name(index); break;
-        case 6: ns = "rtd", name = rtd::query_row_name(index); break;
-        case 7: ns = "rtdb", name = rtdb::query_row_name(index); break;
+        case 0: return kernel_row(kRtd, &KernelNamespace::std, index, out, cap);
+        case 1: return kernel_row(kRtd, &KernelNamespace::paper, index, out, cap);
+        case 2: return kernel_row(kRtf, &KernelNamespace::std, index, out, cap);
+        case 3: return kernel_row(kRtf, &KernelNamespace::paper, index, out, cap);
+        case 4: return kernel_row(kRtdb, &KernelNamespace::std, index, out, cap);
+        case 5: return kernel_row(kRtdb, &KernelNamespace::paper, index, out, cap);
+        case 6: return kernel_row(kRtd, &KernelNamespace::query, index, out, cap);
+        case 7: return kernel_row(kRtdb, &KernelNamespace::query, index, out, cap);
         case 8: {
-            // the namespaces rtamd::launch_paper_finish dispatches to (big-stack
+            // the finish tables rtamd::kernel_namespace hands out (big-stack
             // frames finish with rtd's kernels), rtd's rows first
             int n_rtd = 0;
-            while (rtd::finish_row_name(n_rtd)) ++n_rtd;
-            if (index < n_rtd) ns = "rtd", name = rtd::finish_row_name(index);
-            else ns = "rtf", name = rtf::finish_row_name(index - n_rtd);
-            break;
+            while (rtamd::kernel_namespace(kRtd).finish->row_name(n_rtd)) ++n_rtd;
+            return index < n_rtd ? kernel_row(kRtd, &KernelNamespace::finish, index, out, cap)
+                                 : kernel_row(kRtf, &KernelNamespace::finish, index - n_rtd, out, cap);
         }
         default: return RT_ERR_INVALID_ARG;
     }
-    if (!name) return RT_ERR_INVALID_ARG;
-    std::snprintf(out, (size_t)cap, "%s::%s", ns, name);
-    return RT_OK;
 }
 
 extern "C" int rt_test_paper_order(int32_t* list, int n, const uint32_t* cost, int n_cost) {
@@ -205,81 +238,36 @@ extern "C" int rt_test_jitter_device(int K, int64_t q0, int64_t q1, int64_t firs
 }
 
 extern "C" int rt_test_kernel_name(const rt_scene* s, int mode, int flags, char* out, int cap) {
-    if (!s || !out || cap <= 0) return RT_ERR_INVALID_ARG;
-    rtamd::KernelVariant v;
-    const int rc = scene_variant(s, mode, flags, &v);
-    if (rc != RT_OK) return rc;
-    const rtamd::KernelEntry k = rtamd::trace_kernel(v, mode == RT_MODE_PAPER);
-    if (!k.name) { rtamd::set_last_error("rt_test_kernel_name: no kernel for this variant"); return RT_ERR_UNSUPPORTED; }
-    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
-    return RT_OK;
+    if (mode != RT_MODE_STANDARD && mode != RT_MODE_PAPER) return RT_ERR_INVALID_ARG;
+    return kernel_name("rt_test_kernel_name", s, out, cap, frame_pick(mode, flags),
+                       [=](const KernelVariant& v) { return rtamd::trace_kernel(v, mode == RT_MODE_PAPER); });
 }
 
 extern "C" int rt_test_query_kernel_name(const rt_scene* s, int kind, int flags, char* out, int cap) {
-    if (!s || !out || cap <= 0 || (kind != rtamd::kQueryIsect && kind != rtamd::kQueryOccl)) return RT_ERR_INVALID_ARG;
-    rtamd::KernelVariant v;
-    try {
-        const rt_scene_desc& d = *rt_scene_get_desc(s);
-        const int rc = rtamd::pick_query_variant(rtamd::compile_scene(d), d, flags, &v);
-        if (rc != RT_OK) return rc;
-    } catch (const std::exception& e) {
-        rtamd::set_last_error(std::string("scene compile: ") + e.what());
-        return RT_ERR_INVALID_ARG;
-    }
-    const rtamd::KernelEntry k = rtamd::query_kernel(v, kind);
-    if (!k.name) { rtamd::set_last_error("rt_test_query_kernel_name: no kernel for this variant"); return RT_ERR_UNSUPPORTED; }
-    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
-    return RT_OK;
+    if (kind != rtamd::kQueryIsect && kind != rtamd::kQueryOccl) return RT_ERR_INVALID_ARG;
+    return kernel_name("rt_test_query_kernel_name", s, out, cap, query_pick(rtamd::pick_query_variant, flags),
+                       [=](const KernelVariant& v) { return kernel_in(rtamd::kernel_namespace(v.ns).query, v, kind); });
 }
 
 extern "C" int rt_test_radiance_kernel_name(const rt_scene* s, int flags, char* out, int cap) {
-    if (!s || !out || cap <= 0) return RT_ERR_INVALID_ARG;
-    rtamd::KernelVariant v;
-    try {
-        const rt_scene_desc& d = *rt_scene_get_desc(s);
-        const int rc = rtamd::pick_radiance_variant(rtamd::compile_scene(d), d, flags, &v);
-        if (rc != RT_OK) return rc;
-    } catch (const std::exception& e) {
-        rtamd::set_last_error(std::string("scene compile: ") + e.what());
-        return RT_ERR_INVALID_ARG;
-    }
-    const rtamd::KernelEntry k = rtamd::radiance_kernel(v);
-    if (!k.name) { rtamd::set_last_error("rt_test_radiance_kernel_name: no kernel for this variant"); return RT_ERR_UNSUPPORTED; }
-    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
-    return RT_OK;
-}
-
-extern "C" int rt_test_radiance_kernel_row(int table, int index, char* out, int cap) {
-    if (!out || cap <= 0 || index < 0 || (table != 0 && table != 1)) return RT_ERR_INVALID_ARG;
-    const char* name = table ? rtdb::radiance_row_name(index) : rtd::radiance_row_name(index);
-    if (!name) return RT_ERR_INVALID_ARG;
-    std::snprintf(out, (size_t)cap, "%s::%s", table ? "rtdb" : "rtd", name);
-    return RT_OK;
+    return kernel_name("rt_test_radiance_kernel_name", s, out, cap, query_pick(rtamd::pick_radiance_variant, flags),
+                       [](const KernelVariant& v) { return kernel_in(rtamd::kernel_namespace(v.ns).radiance, v); });
 }
 
 extern "C" int rt_test_shade_kernel_name(const rt_scene* s, int flags, char* out, int cap) {
-    if (!s || !out || cap <= 0) return RT_ERR_INVALID_ARG;
-    rtamd::KernelVariant v;
-    try {
-        const rt_scene_desc& d = *rt_scene_get_desc(s);
-        const int rc = rtamd::pick_shade_variant(rtamd::compile_scene(d), d, flags, &v);
-        if (rc != RT_OK) return rc;
-    } catch (const std::exception& e) {
-        rtamd::set_last_error(std::string("scene compile: ") + e.what());
-        return RT_ERR_INVALID_ARG;
-    }
-    const rtamd::KernelEntry k = rtamd::shade_kernel(v);
-    if (!k.name) { rtamd::set_last_error("rt_test_shade_kernel_name: no kernel for this variant"); return RT_ERR_UNSUPPORTED; }
-    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
-    return RT_OK;
+    return kernel_name("rt_test_shade_kernel_name", s, out, cap, query_pick(rtamd::pick_shade_variant, flags),
+                       [](const KernelVariant& v) { return kernel_in(rtamd::kernel_namespace(v.ns).shade, v); });
+}
+
+// (table 0: rtd's, 1: rtdb's)
+extern "C" int rt_test_radiance_kernel_row(int table, int index, char* out, int cap) {
+    if (table != 0 && table != 1) return RT_ERR_INVALID_ARG;
+    return kernel_row(table ? KernelVariant::kRtdb : KernelVariant::kRtd, &KernelNamespace::radiance, index, out, cap);
 }
 
 extern "C" int rt_test_shade_kernel_row(int table, int index, char* out, int cap) {
-    if (!out || cap <= 0 || index < 0 || (table != 0 && table != 1)) return RT_ERR_INVALID_ARG;
-    const char* name = table ? rtdb::shade_row_name(index) : rtd::shade_row_name(index);
-    if (!name) return RT_ERR_INVALID_ARG;
-    std::snprintf(out, (size_t)cap, "%s::%s", table ? "rtdb" : "rtd", name);
-    return RT_OK;
+    if (table != 0 && table != 1) return RT_ERR_INVALID_ARG;
+    return kernel_row(table ? KernelVariant::kRtdb : KernelVariant::kRtd, &KernelNamespace::shade, index, out, cap);
 }
 
 extern "C" int rt_test_kernel_info(const rt_scene* s, int mode, int flags, int32_t* out) {
@@ -288,7 +276,8 @@ extern "C" int rt_test_kernel_info(const rt_scene* s, int mode, int flags, int32
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RT_ERR_NO_DEVICE;
     rtamd::KernelVariant v;
     // (the non-counting, untimed variant, whatever the flags say)
-    const int rc = scene_variant(s, mode, flags & ~RT_FLAG_COUNT_OPS, &v);
+    if (mode != RT_MODE_STANDARD && mode != RT_MODE_PAPER) return RT_ERR_INVALID_ARG;
+    const int rc = scene_variant(s, frame_pick(mode, flags & ~RT_FLAG_COUNT_OPS), &v);
     if (rc != RT_OK) return rc;
     const bool paper = mode == RT_MODE_PAPER;
     const void* fn = rtamd::trace_kernel(v, paper).fn;

@@ -64,26 +64,40 @@ int wave_cull_min() {
 
 const char* variant_ns_name(int ns) { return ns == KernelVariant::kRtdb ? "rtdb" : ns == KernelVariant::kRtf ? "rtf" : "rtd"; }
 
-int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int flags, bool bvh_enabled,
-                 KernelVariant* out) {
-    KernelVariant v;
-    const bool fp32 = (flags & RT_FLAG_FP32) != 0;
+namespace {
+// What every pick_* shares.  frames_if_secondary: whether the trace keeps
+// reflection / refraction frames (a standard frame or a radiance query: then
+// recursion_limit - 1 of them when the scene is secondary).  Sets secondary, ns
+// (the stack tier), eager and deep.
+int pick_common(const CompiledScene& cs, const rt_scene_desc& d, bool frames_if_secondary, bool fp32, KernelVariant& v) {
     for (int i = 0; i < d.n_materials; ++i)
         if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) v.secondary = true;
     if (d.recursion_limit < 2) v.secondary = false;   // depth < limit-1 never holds (tracer.cpp:38,51)
-    const int frames = (v.secondary && mode == RT_MODE_STANDARD) ? d.recursion_limit - 1 : 0;
     bool big = false;
-    {
-        const int rc = stack_tier(cs, d, frames, fp32, &big);
-        if (rc != RT_OK) return rc;
-    }
+    const int rc = stack_tier(cs, d, frames_if_secondary && v.secondary ? d.recursion_limit - 1 : 0, fp32, &big);
+    if (rc != RT_OK) return rc;
     v.ns = big ? KernelVariant::kRtdb : fp32 ? KernelVariant::kRtf : KernelVariant::kRtd;
-    v.count_ops = (flags & RT_FLAG_COUNT_OPS) != 0;
     // the big-stack build has only the general variants (every feature);
     // eager scenes always use D; the lean kernels carry no directional-light
     // code: such scenes take the general (D) variants
     v.eager = big || cs.has_eager;
     v.deep = v.eager || cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
+    return RT_OK;
+}
+// The plain variants: lean (not D) kernels of plain scenes, unless RT_PLAIN=0
+bool pick_plain(const CompiledScene& cs, const KernelVariant& v) {
+    static const bool plain_on = env_on("RT_PLAIN");
+    return !v.deep && plain_on && plain_scene(cs);
+}
+}  // namespace
+
+int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int flags, bool bvh_enabled,
+                 KernelVariant* out) {
+    KernelVariant v;
+    const bool fp32 = (flags & RT_FLAG_FP32) != 0;
+    const int rc = pick_common(cs, d, mode == RT_MODE_STANDARD, fp32, v);
+    if (rc != RT_OK) return rc;
+    v.count_ops = (flags & RT_FLAG_COUNT_OPS) != 0;
     if (!v.deep) {
         int n_bounded = 0;
         for (const auto& o : cs.objs)
@@ -94,9 +108,8 @@ int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int 
         // the plain variants: FP64 only, never op-counting; standard-mode
         // reflection / refraction without wave culls runs the general kernel
         // k_std<false, false, true>, which has none
-        static const bool plain_on = env_on("RT_PLAIN");
         const bool general = mode == RT_MODE_STANDARD && v.secondary && v.wv == 0;
-        v.plain = !general && !fp32 && !v.count_ops && plain_on && plain_scene(cs);
+        v.plain = !general && !fp32 && !v.count_ops && pick_plain(cs, v);
     }
     *out = v;
     return RT_OK;
@@ -118,16 +131,10 @@ int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flag
     int rc = check_query_flags(flags);
     if (rc != RT_OK) return rc;
     KernelVariant v;
-    bool big = false;
-    rc = stack_tier(cs, d, 0, false, &big);
+    rc = pick_common(cs, d, false, false, v);
     if (rc != RT_OK) return rc;
-    v.ns = big ? KernelVariant::kRtdb : KernelVariant::kRtd;
-    // (as pick_variant: the big-stack build has only the general variant, eager
-    // scenes always use D, scenes with directional lights take the D variants)
-    v.eager = big || cs.has_eager;
-    v.deep = v.eager || cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
-    static const bool plain_on = env_on("RT_PLAIN");
-    v.plain = !v.deep && plain_on && plain_scene(cs);
+    v.secondary = false;   // (a query traces one ray)
+    v.plain = pick_plain(cs, v);
     *out = v;
     return RT_OK;
 }
@@ -141,18 +148,10 @@ int pick_radiance_variant(const CompiledScene& cs, const rt_scene_desc& d, int f
     int rc = check_query_flags(flags);
     if (rc != RT_OK) return rc;
     KernelVariant v;
-    for (int i = 0; i < d.n_materials; ++i)
-        if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) v.secondary = true;
-    if (d.recursion_limit < 2) v.secondary = false;   // (as pick_variant)
-    bool big = false;
-    rc = stack_tier(cs, d, v.secondary ? d.recursion_limit - 1 : 0, false, &big);
+    rc = pick_common(cs, d, true, false, v);
     if (rc != RT_OK) return rc;
-    v.ns = big ? KernelVariant::kRtdb : KernelVariant::kRtd;
-    v.eager = big || cs.has_eager;
-    v.deep = v.eager || cs.max_ivl_depth > 2 || d.n_dir_lights > 0;
     if (v.eager) v.secondary = true;   // (the general row: the only eager one)
-    static const bool plain_on = env_on("RT_PLAIN");
-    v.plain = !v.deep && plain_on && plain_scene(cs);
+    v.plain = pick_plain(cs, v);
     *out = v;
     return RT_OK;
 }

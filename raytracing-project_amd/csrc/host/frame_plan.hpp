@@ -76,7 +76,7 @@ int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flag
 // the kernel's scene walks are the shadow rays' Scene::occluded calls (E, D,
 // PL and the stack tier of a query without recursion frames; D also carries
 // the directional lights' code).  Looked up in the shade tables (rt_launch.hpp
-// shade_kernel).
+// KernelNamespace::shade).
 int pick_shade_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
 
 // The variant a radiance query (rt_query_radiance: Tracer::trace of caller-given

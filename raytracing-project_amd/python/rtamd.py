@@ -201,22 +201,17 @@ def amd_lib():
                                                       C.c_void_p, C.c_void_p, C.POINTER(Stats)]
             lib.rt_query_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                                      C.c_void_p, C.POINTER(Stats)]
-            lib.rt_test_query_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
         if hasattr(lib, "rt_query_radiance"):   # (absent only in RTAMD_LIB builds of older sources)
             lib.rt_query_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                               C.POINTER(Stats)]
             lib.rt_query_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                                      C.c_void_p, C.POINTER(Stats)]
-            lib.rt_test_radiance_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
-            lib.rt_test_radiance_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
         if hasattr(lib, "rt_query_shade"):   # (likewise)
             lib.rt_query_shade.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Stats)]
             lib.rt_query_shade_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.POINTER(Stats)]
-            lib.rt_test_shade_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
-            lib.rt_test_shade_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
         if hasattr(lib, "rt_camera_rays"):   # (likewise)
             lib.rt_camera_rays.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                            C.c_void_p, C.POINTER(Stats)]
@@ -505,14 +500,31 @@ def sphere_nodes_at(scene: Scene, centres) -> list[int]:
     return out
 
 
+def _kernel_name(hook: str, scene: Scene, *args: int) -> tuple[int, str]:
+    """(status, "ns::kernel") from the rt_test_*_kernel_name hook `hook` of (scene, *args)."""
+    fn = getattr(amd_lib(), hook)
+    fn.argtypes = [C.c_void_p] + [C.c_int] * len(args) + [C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(160)
+    rc = fn(scene.handle, *args, buf, 160)
+    return rc, buf.value.decode()
+
+
+def _kernel_rows(hook: str, table: int) -> list[str]:
+    """The rows ("ns::kernel") of table `table` from the rt_test_*_kernel_row hook
+    `hook`, read from the table the launcher searches."""
+    fn = getattr(amd_lib(), hook)
+    fn.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(160)
+    out = []
+    while fn(table, len(out), buf, 160) == RT_OK:
+        out.append(buf.value.decode())
+    return out
+
+
 def kernel_name(scene: Scene, mode: int, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
     """rt_test_kernel_name: (status, "ns::kernel") of the trace kernel a frame
     of this scene, mode and flags launches.  Host only."""
-    lib = amd_lib()
-    lib.rt_test_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
-    buf = C.create_string_buffer(160)
-    rc = lib.rt_test_kernel_name(scene.handle, mode, flags, buf, 160)
-    return rc, buf.value.decode()
+    return _kernel_name("rt_test_kernel_name", scene, mode, flags)
 
 
 OBJ_KINDS = ("sphere", "half", "poke", "chain", "eager", "never", "group")
@@ -551,13 +563,7 @@ def kernel_rows(table: int) -> list[str]:
     """rt_test_kernel_row: the rows ("ns::kernel") of launch table `table`
     (an index into KERNEL_TABLES), read from the table the launcher searches.
     Host only."""
-    lib = amd_lib()
-    lib.rt_test_kernel_row.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
-    buf = C.create_string_buffer(160)
-    out = []
-    while lib.rt_test_kernel_row(table, len(out), buf, 160) == RT_OK:
-        out.append(buf.value.decode())
-    return out
+    return _kernel_rows("rt_test_kernel_row", table)
 
 
 def launch_log(on: bool) -> None:
@@ -812,9 +818,7 @@ def query_intersect_device(scene: Scene, rays_dev: DeviceBuffer, n: int, hits_de
 def query_kernel_name(scene: Scene, kind: int, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
     """rt_test_query_kernel_name: (status, "ns::kernel") of the kernel a query
     of kind 0 (intersect) / 1 (occluded) launches.  Host only."""
-    buf = C.create_string_buffer(160)
-    rc = amd_lib().rt_test_query_kernel_name(scene.handle, kind, flags, buf, 160)
-    return rc, buf.value.decode()
+    return _kernel_name("rt_test_query_kernel_name", scene, kind, flags)
 
 
 def query_radiance(scene: Scene, origins, dirs, flags: int = RT_FLAG_NONE, stats: Stats | None = None) -> np.ndarray:
@@ -848,9 +852,7 @@ def query_radiance_device(scene: Scene, rays_dev: DeviceBuffer, n: int, rgb_dev:
 def radiance_kernel_name(scene: Scene, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
     """rt_test_radiance_kernel_name: (status, "ns::kernel") of the kernel a
     radiance query of this scene and flags launches.  Host only."""
-    buf = C.create_string_buffer(160)
-    rc = amd_lib().rt_test_radiance_kernel_name(scene.handle, flags, buf, 160)
-    return rc, buf.value.decode()
+    return _kernel_name("rt_test_radiance_kernel_name", scene, flags)
 
 
 RADIANCE_TABLES = ("rtd radiance", "rtdb radiance")
@@ -859,12 +861,7 @@ RADIANCE_TABLES = ("rtd radiance", "rtdb radiance")
 def radiance_rows(table: int) -> list[str]:
     """rt_test_radiance_kernel_row: the rows ("ns::kernel") of radiance launch
     table `table` (an index into RADIANCE_TABLES).  Host only."""
-    lib = amd_lib()
-    buf = C.create_string_buffer(160)
-    out = []
-    while lib.rt_test_radiance_kernel_row(table, len(out), buf, 160) == RT_OK:
-        out.append(buf.value.decode())
-    return out
+    return _kernel_rows("rt_test_radiance_kernel_row", table)
 
 
 def _light_array(lights):
@@ -935,9 +932,7 @@ def query_shade_device(scene: Scene, hits_dev: DeviceBuffer, wo_dev: DeviceBuffe
 def shade_kernel_name(scene: Scene, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
     """rt_test_shade_kernel_name: (status, "ns::kernel") of the kernel a
     shading query of this scene and flags launches.  Host only."""
-    buf = C.create_string_buffer(160)
-    rc = amd_lib().rt_test_shade_kernel_name(scene.handle, flags, buf, 160)
-    return rc, buf.value.decode()
+    return _kernel_name("rt_test_shade_kernel_name", scene, flags)
 
 
 SHADE_TABLES = ("rtd shade", "rtdb shade")
@@ -946,12 +941,7 @@ SHADE_TABLES = ("rtd shade", "rtdb shade")
 def shade_rows(table: int) -> list[str]:
     """rt_test_shade_kernel_row: the rows ("ns::kernel") of shade launch
     table `table` (an index into SHADE_TABLES).  Host only."""
-    lib = amd_lib()
-    buf = C.create_string_buffer(160)
-    out = []
-    while lib.rt_test_shade_kernel_row(table, len(out), buf, 160) == RT_OK:
-        out.append(buf.value.decode())
-    return out
+    return _kernel_rows("rt_test_shade_kernel_row", table)
 
 
 def _camera_of(cam_or_scene) -> Camera:
@@ -1110,7 +1100,10 @@ def paper_resolve_device(hits_dev: DeviceBuffer, mask_dev: DeviceBuffer | None, 
 
 
 def camera_chunk_rays(n: int) -> None:
-    """rt_test_camera_chunk_rays: rays per staging chunk of camera_rays (0: the default)."""
+    """rt_test_camera_chunk_rays: items per staging chunk of the batched calls'
+    host forms - rays of camera_rays (whole rows, at least one), rays of
+    query_intersect / query_occluded / query_radiance, hits of query_shade
+    (0: the default, 2^20)."""
     _ok(amd_lib().rt_test_camera_chunk_rays(n), "rt_test_camera_chunk_rays")
 
 

@@ -375,6 +375,38 @@ def test_host_batch_larger_than_one_chunk(gpu):
     assert np.array_equal(q_occl(gpu, c.scene, segs), np.tile(small_occ, reps)[:n])
 
 
+def test_small_host_chunks_are_the_default_chunk(gpu):
+    """The host forms' chunk forced to 100 rays (rt_test_camera_chunk_rays sets
+    the one chunk size of every batched call): 1000 rays cross ten chunks, each
+    ending in a partial wave (100 is no multiple of 64) whose tail lanes replay
+    a ray and must not store.  The same bytes and stats as at the default chunk."""
+    c = case(gpu, "config4")
+    n = 1000
+    reps = -(-n // len(c.rays))
+    rays, segs = np.tile(c.rays, reps)[:n], np.tile(c.seg_rays, reps)[:n]
+
+    def run():
+        si, so = gpu.Stats(), gpu.Stats()
+        hits, occ = q_isect(gpu, c.scene, rays, stats=si), q_occl(gpu, c.scene, segs, stats=so)
+        return (hits.records.tobytes(), hits.hit.tobytes(), occ.tobytes(),
+                [(s.rays_intersect, s.rays_occluded, s.rays_traced) for s in (si, so)])
+
+    want = run()
+    gpu.camera_chunk_rays(100)
+    try:
+        gpu.launch_log(True)
+        got = run()
+        launches = gpu.launch_log_get()
+    finally:
+        gpu.launch_log(False)
+        gpu.camera_chunk_rays(0)
+    assert len(launches) == 2 * 10   # (ten chunks a call)
+    assert got == want
+    assert want[3] == [(n, 0, n), (0, n, n)]
+    hit = np.frombuffer(want[1], dtype=bool)
+    assert hit.any() and not hit.all()   # (the optional mask says something)
+
+
 # ---------------------------------------------------- degenerate directions
 def test_zero_length_direction_is_plus_y(gpu):
     """Ray::Ray normalises through Dir3::normalized (core.h:95-101, 278): a

@@ -278,6 +278,37 @@ def test_host_batch_larger_than_one_chunk(gpu):
     assert st.rays_occluded == reps * s_all.rays_occluded + s_rest.rays_occluded
 
 
+def test_small_host_chunks_are_the_default_chunk(gpu):
+    """The host form's chunk forced to 100 rays (rt_test_camera_chunk_rays sets
+    the one chunk size of every batched call) on a scene that reflects and
+    refracts: 1000 rays cross ten chunks, each ending in a partial wave whose
+    tail lanes replay a ray and must neither store nor count, and the counters
+    accumulate over the chunks and the bounces.  The same bytes and counts as
+    at the default chunk, and the oracle's counts."""
+    r = ref_of(gpu, "torture/reflect_refract")
+    d = r.sc.desc
+    assert any(d.materials[i].kr > 0.0 or d.materials[i].kt > 0.0 for i in range(d.n_materials))
+    n = 1000
+    reps = -(-n // len(r))
+    o, dirs = np.tile(r.o, (reps, 1))[:n], np.tile(r.d, (reps, 1))[:n]
+    s0, s1 = gpu.Stats(), gpu.Stats()
+    want = gpu.query_radiance(r.sc, o, dirs, stats=s0)
+    gpu.camera_chunk_rays(100)
+    try:
+        gpu.launch_log(True)
+        got = gpu.query_radiance(r.sc, o, dirs, stats=s1)
+        launches = gpu.launch_log_get()
+    finally:
+        gpu.launch_log(False)
+        gpu.camera_chunk_rays(0)
+    assert len(launches) == 10 and all("k_radiance" in k for k in launches)   # (ten chunks)
+    assert got.tobytes() == want.tobytes()
+    counts = (int(np.tile(r.ni, reps)[:n].sum()), int(np.tile(r.no, reps)[:n].sum()))
+    for s in (s0, s1):
+        assert (s.rays_intersect, s.rays_occluded, s.rays_traced) == (counts[0], counts[1], sum(counts))
+    assert counts[0] > n   # (bounces were traced)
+
+
 # ------------------------------------------------ 7. degenerate directions, ranges
 def test_zero_length_direction_and_unread_ranges(gpu):
     """A direction of length <= 1e-6 is (0, 1, 0) (core.h:95-101, 278); tmin and

@@ -437,6 +437,52 @@ def test_host_batch_larger_than_one_chunk(gpu):
     assert st.rays_intersect == 0 and st.rays_traced == st.rays_occluded
 
 
+def test_small_host_chunks_are_the_default_chunk(gpu):
+    """The host form's chunk forced to 100 hits (rt_test_camera_chunk_rays sets
+    the one chunk size of every batched call): 1000 hits cross ten chunks, each
+    ending in a partial wave.  Once with a mask that blanks a whole chunk, once
+    with the call's own lights (their upload must outlive the first chunk),
+    then without lights again (the scene's own still shade).  The same bytes
+    and counts as at the default chunk."""
+    r = shade_ref(gpu, "config4")
+    n = 1000
+    reps = -(-n // len(r))
+    H, wo = np.tile(r.H, reps)[:n], np.tile(r.wo, (reps, 1))[:n]
+    hit = np.tile(r.hit, reps)[:n]
+    blank = hit.copy()
+    blank[300:400] = False   # (the fourth chunk of 100)
+    lights = override_lights("config4", 3)
+    d = r.sc.desc
+    assert len(lights) >= 2 and lights != [(list(d.lights[i].pos), list(d.lights[i].intensity)) for i in range(d.n_lights)]
+
+    def run():
+        out = []
+        for mask, lg in ((blank, None), (hit, lights), (hit, None)):
+            st = gpu.Stats()
+            rgb = gpu.query_shade(r.sc, H, wo, mask.astype(np.uint8), lg, None, 0, st)
+            out.append((rgb.tobytes(), (st.rays_intersect, st.rays_occluded, st.rays_traced)))
+        return out
+
+    want = run()
+    gpu.camera_chunk_rays(100)
+    try:
+        gpu.launch_log(True)
+        got = run()
+        launches = gpu.launch_log_get()
+    finally:
+        gpu.launch_log(False)
+        gpu.camera_chunk_rays(0)
+    assert len(launches) == 3 * 10 and all("k_shade" in k for k in launches)   # (ten chunks a call)
+    assert got == want
+    rgb = [np.frombuffer(b, dtype=np.float64).reshape(n, 3) for b, _ in want]
+    assert rgb[0][300:400].tobytes() == np.tile(r.background, (100, 1)).tobytes()
+    assert rgb[1].tobytes() != rgb[2].tobytes()   # (the call's lights, then the scene's own)
+    # the scene's own lights: this file's reference for them, and the oracle's count
+    assert np.abs(rgb[2][hit] - np.tile(r.rgb, (reps, 1))[:n][hit]).max() <= TOL
+    assert want[2][1] == (0, int(np.tile(r.no, reps)[:n][hit].sum()), int(np.tile(r.no, reps)[:n][hit].sum()))
+    assert want[0][1][1] == int(np.tile(r.no, reps)[:n][blank].sum()) > 0
+
+
 # ----------------------------------------------------------------- 10. residency
 def test_frame_shade_query_frame_share_the_resident_scene(gpu):
     """Frame -> shade query -> intersect query -> frame of one scene: the
