@@ -27,6 +27,9 @@
  *                               raytracer/src/scene.cpp:10-24
  *   rt_query_occluded        <- Scene::occluded, a batch of rays
  *                               raytracer/src/scene.cpp:33-42
+ *   rt_query_node_intersect  <- Primitive::intersect of one node, a batch of rays
+ *   rt_query_node_interval   <- Primitive::interval of one node, a batch of rays
+ *                               raytracer/src/geometry.h:62-75 (and every override)
  *   rt_query_radiance        <- Tracer::trace, a batch of rays
  *                               raytracer/src/tracer.cpp:12-73
  *   rt_query_shade           <- shade_lambert_phong, a batch of hits
@@ -76,7 +79,9 @@ extern "C" {
                                rt_camera_rays_device / rt_resolve_samples /
                                rt_resolve_samples_device, and the paper-frame links
                                rt_rays_wo / rt_rays_wo_device / rt_paper_resolve /
-                               rt_paper_resolve_device) */
+                               rt_paper_resolve_device, and the node queries
+                               rt_query_node_intersect / rt_query_node_interval and
+                               their *_device forms) */
 
 /* ---------------------------------------------------------------- errors */
 enum rt_status {
@@ -452,6 +457,74 @@ int rt_query_intersect_device(const rt_scene* s, const rt_ray* rays_dev, size_t 
                               uint8_t* hit_mask_dev, void* hip_stream, rt_stats* stats);
 int rt_query_occluded_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, uint8_t* occluded_dev,
                              void* hip_stream, rt_stats* stats);
+
+/* ------------------------------------------------------ node queries
+ * Primitive::intersect and Primitive::interval (geometry.h:62-75), the virtual
+ * pair every sphere, half-space, pokeball, transform and CSG node overrides,
+ * of ONE node of the scene graph for a batch of caller-given rays: per-object
+ * picking with the caller's own range whatever stands in front, inside /
+ * outside classification of points (the reference's rule is enter.t < 1e-6 &&
+ * exit.t > 1e-6, csg.cpp:92-94), thickness and X-ray images (exit.t - enter.t),
+ * voxelisation and volume estimates of a CSG solid, collision sweeps against
+ * one body, a preview of one operand of a CSG tree.
+ *
+ * node is an index into rt_scene_get_desc(s)->nodes: any node, not only a
+ * top-level object's (objects[k] is top-level object k's); outside
+ * [0, n_nodes) it is RT_ERR_INVALID_ARG.  The scene's other objects, its
+ * lights and its camera play no part.  The ray is Ray(o, d) as for the other
+ * queries (core.h:278).
+ *
+ * hits_host[i] = Primitive::intersect(node, Ray(rays_host[i].o, rays_host[i].d),
+ * rays_host[i].tmin, rays_host[i].tmax): the reference's Hit exactly as
+ * rt_query_intersect reports one (mat = -1 on a null material; all zero with
+ * mat = -1 on a miss; hit_mask_host, which may be NULL, tells them apart).  A
+ * degenerate Scaling never hits (transform.cpp:97).
+ *
+ * (enter_host[i], exit_host[i]) = Primitive::interval(node, Ray(rays_host[i].o,
+ * rays_host[i].d)); tmin and tmax of rt_ray are NOT READ, interval has no
+ * range.  enter.t is tEnter and exit.t is tExit, the call's out-parameters -
+ * not the reference records' own Hit::t, which under a transform keeps a stale
+ * local value nothing reads.  p, n, mat and front_face are what the reference
+ * leaves in enterHit / exitHit, the odd cases included: a half-space's infinite
+ * end has t = -inf / +inf, p = the ray's origin and the plane's face normal
+ * (geometry.cpp:117-147); a CSG that contains the origin enters at t = 0 with
+ * p = o, n = (0, 0, 0), the origin material of csg.cpp:120 and front_face = 1;
+ * a difference's re-faced normals follow csg.cpp:139-150; a transform maps p
+ * and n back and projects both t (transform.cpp:55-82).  Only the FIRST inside
+ * interval along the ray is reported, as in the reference (csg.cpp:151): a
+ * caller walks the further spans by querying again from beyond exit.t.  Where
+ * interval returns false both records are zero with mat = -1 and
+ * ok_mask_host[i] = 0.  ok_mask_host may be NULL, and so may either of
+ * enter_host / exit_host, but not all three.  enter_host with ok_mask_host is
+ * valid input for rt_query_shade[_device] as it is.
+ *
+ * Non-finite rays get the reference's answer and change no other ray's bytes,
+ * as for the ray queries above.  flags: RT_FLAG_NONE or RT_FLAG_NO_CULL
+ * (identical bytes: these kernels have no cull; RT_FLAG_NO_BVH /
+ * RT_FLAG_FORCE_BVH have no effect); RT_FLAG_FP32 and RT_FLAG_COUNT_OPS are
+ * RT_ERR_UNSUPPORTED, as is a node whose OWN subtree nests deeper than the
+ * device stacks (the frames' limits and message; refused on the host before
+ * any launch).  n == 0 is RT_OK without a launch; every argument check comes
+ * before any device work.  stats (may be NULL): rays_intersect = rays_traced =
+ * n for both calls (one primitive query per ray), ms_kernel, ms_total.  Per
+ * ray 64 B cross to the device and 64 B (intersect) or 128 B (interval) plus
+ * 1 B back, in chunks of bounded size.  Uses the current HIP device and shares
+ * its resident scene copy with the frames and the other queries, which a node
+ * query leaves as it was; the node's compiled program is built and uploaded
+ * the first time that node is queried and kept with the resident scene (that
+ * first query's compile counts in rt_setup_times[0]).  Waits for an open frame
+ * of the device; blocks until done. */
+int rt_query_node_intersect(const rt_scene* s, int node, const rt_ray* rays_host, size_t n, int flags,
+                            rt_hit* hits_host, uint8_t* hit_mask_host, rt_stats* stats);
+int rt_query_node_interval(const rt_scene* s, int node, const rt_ray* rays_host, size_t n, int flags,
+                           rt_hit* enter_host, rt_hit* exit_host, uint8_t* ok_mask_host, rt_stats* stats);
+/* The same with rays and results already on the device, enqueued on
+ * hip_stream (NULL = the default stream); blocks until done. */
+int rt_query_node_intersect_device(const rt_scene* s, int node, const rt_ray* rays_dev, size_t n, int flags,
+                                   rt_hit* hits_dev, uint8_t* hit_mask_dev, void* hip_stream, rt_stats* stats);
+int rt_query_node_interval_device(const rt_scene* s, int node, const rt_ray* rays_dev, size_t n, int flags,
+                                  rt_hit* enter_dev, rt_hit* exit_dev, uint8_t* ok_mask_dev, void* hip_stream,
+                                  rt_stats* stats);
 
 /* -------------------------------------------------- radiance queries
  * Tracer::trace(const Ray&) (tracer.cpp:12-73) for a batch of caller-given

@@ -111,12 +111,27 @@ int rt_test_radiance_kernel_row(int table, int index, char* out, int cap);
 int rt_test_shade_kernel_name(const struct rt_scene* s, int flags, char* out, int cap);
 int rt_test_shade_kernel_row(int table, int index, char* out, int cap);
 
+/* The same for a node query (rt_query_node_intersect / rt_query_node_interval)
+ * of node `node`: kind 0 the intersect kernel, 1 the interval one (e.g.
+ * "rtdb::k_node_ivl<true>"): the query's own choice (compile_node_program +
+ * frame_plan.hpp pick_node_variant) looked up in the node table, so the nodes
+ * and flags a query refuses are refused here too; and row `index` of node
+ * launch table `table` (0 rtd, 1 rtdb).  Host only. */
+int rt_test_node_kernel_name(const struct rt_scene* s, int node, int kind, int flags, char* out, int cap);
+int rt_test_node_kernel_row(int table, int index, char* out, int cap);
+/* That node's own program (scene_compile.hpp compile_node_program): returns
+ * its op count (<0: an rt_status) and writes (op, node, top, csg_op) of the
+ * first min(count, cap) ops to ops_out[4 * i ..] (ops_out may be NULL with
+ * cap 0) and, when depths_out2 is set, {max_ray_depth, max_ivl_depth} of the
+ * program itself.  Host only. */
+int rt_test_node_program(const struct rt_scene* s, int node, int kind, int32_t* ops_out, int cap, int32_t* depths_out2);
+
 /* The launch log: which kernels ran.  rt_test_kernel_name above is the plan
  * for a frame whose wave BVH is on and untimed; the frame itself may drop the
  * BVH (its trial frames) or launch the timed build of a paper kernel (the
  * first frame of a scene and shape).  The log records what the launchers of
  * rt_kernels.hpp / rt_query_kernels.hpp / rt_radiance_kernels.hpp /
- * rt_shade_kernels.hpp were asked for, host side only.
+ * rt_shade_kernels.hpp / rt_node_kernels.hpp were asked for, host side only.
  * on != 0: clear the log and start recording; 0: stop.  Process-wide,
  * thread-safe; while recording is off a launch pays one relaxed atomic load. */
 int rt_test_launch_log(int on);

@@ -163,6 +163,24 @@ struct ShadeParams {
     unsigned long long* counters;
 };
 
+// A batch of node queries (rt_query_node_intersect / rt_query_node_interval):
+// ray i of rays[0, n) is lane i % 64 of wave i / 64, queried against ONE node
+// of the scene graph.  A leaf row reads the leaf `node`; a program row runs
+// ops[0, n_ops) (compile_node_program: a buffer of its own, not the scene's
+// SceneView::ops).  Intersect: enter[i] the hit, mask[i] (may be null) 1 / 0;
+// interval: enter[i] / exit[i] (either may be null) the enterHit / exitHit with
+// t = tEnter / tExit, mask[i] (may be null) interval()'s return value.
+struct NodeParams {
+    const rt_ray* rays;
+    size_t n;
+    rt_hit* enter;
+    rt_hit* exit;
+    uint8_t* mask;
+    const DevOp* ops;
+    int n_ops;
+    int node;
+};
+
 // Paper mode's output alphabet (tracer.cpp:258-281): every pixel is grey
 // (r = g = b) and a function of the edge strength - the max of the constants
 // {0.9, 0.6, 0.5, 0.3} over the neighbour tests, or 0, halved when a
@@ -202,7 +220,7 @@ struct KernelEntry {
 void note_launch(const char* ns, const char* name);
 
 // One kernel table of one namespace as the host sees it (the rows: rt_kernels.hpp,
-// rt_query_kernels.hpp, rt_radiance_kernels.hpp, rt_shade_kernels.hpp, each in
+// rt_query_kernels.hpp, rt_radiance_kernels.hpp, rt_shade_kernels.hpp, rt_node_kernels.hpp, each in
 // the form of rt_kernel_table.hpp and in translation units of its own).
 // kind: the query table's rtamd::kQueryIsect / kQueryOccl; grid: the paper
 // tables' (the host's 16x16-pixel units; the finish pass's x extent); a table
@@ -225,6 +243,7 @@ struct KernelNamespace {
     const KernelTable<QueryParams>* query;
     const KernelTable<RadianceParams>* radiance;
     const KernelTable<ShadeParams>* shade;
+    const KernelTable<NodeParams>* node;   // kind: kNodeIsect / kNodeIvl (scene_compile.hpp)
 };
 
 }  // namespace rtamd
@@ -239,6 +258,7 @@ struct KernelNamespace {
     const rtamd::KernelTable<rtamd::QueryParams>& query_table();       \
     const rtamd::KernelTable<rtamd::RadianceParams>& radiance_table(); \
     const rtamd::KernelTable<rtamd::ShadeParams>& shade_table();       \
+    const rtamd::KernelTable<rtamd::NodeParams>& node_table();         \
     }
 RT_DECLARE_TABLES(rtd)
 RT_DECLARE_TABLES(rtf)    // (defines the frame tables only)
@@ -247,16 +267,16 @@ RT_DECLARE_TABLES(rtdb)
 
 namespace rtamd {
 // KernelVariant::ns -> its namespace: the one place that choice is written.
-// rtf has no query, radiance or shade kernels (no FP32 build of them: the
+// rtf has no query, radiance, shade or node kernels (no FP32 build of them: the
 // pick_*_variant of those families never pick it); the big-stack build has no
 // finish pass of its own (k_paper_finish reads records only): rtd's.
 inline const KernelNamespace& kernel_namespace(int ns) {
     static const KernelNamespace k[] = {
         {"rtd", &rtd::std_table(), &rtd::paper_table(), &rtd::finish_table(), &rtd::query_table(),
-         &rtd::radiance_table(), &rtd::shade_table()},
-        {"rtf", &rtf::std_table(), &rtf::paper_table(), &rtf::finish_table(), nullptr, nullptr, nullptr},
+         &rtd::radiance_table(), &rtd::shade_table(), &rtd::node_table()},
+        {"rtf", &rtf::std_table(), &rtf::paper_table(), &rtf::finish_table(), nullptr, nullptr, nullptr, nullptr},
         {"rtdb", &rtdb::std_table(), &rtdb::paper_table(), &rtd::finish_table(), &rtdb::query_table(),
-         &rtdb::radiance_table(), &rtdb::shade_table()}};
+         &rtdb::radiance_table(), &rtdb::shade_table(), &rtdb::node_table()}};
     static_assert(KernelVariant::kRtd == 0 && KernelVariant::kRtf == 1 && KernelVariant::kRtdb == 2, "k's order");
     return k[ns == KernelVariant::kRtf || ns == KernelVariant::kRtdb ? ns : KernelVariant::kRtd];
 }
@@ -294,6 +314,9 @@ inline hipError_t launch_radiance(const KernelVariant& v, hipStream_t st, const 
 }
 inline hipError_t launch_shade(const KernelVariant& v, hipStream_t st, const SceneView& V, const ShadeParams& P) {
     return launch_in(kernel_namespace(v.ns).shade, v, 0, dim3(), st, V, P);
+}
+inline hipError_t launch_node(const KernelVariant& v, int kind, hipStream_t st, const SceneView& V, const NodeParams& P) {
+    return launch_in(kernel_namespace(v.ns).node, v, kind, dim3(), st, V, P);
 }
 // The variant's trace kernel of `mode` ({nullptr, nullptr}: none), and its launch shape
 inline KernelEntry trace_kernel(const KernelVariant& v, bool paper) {

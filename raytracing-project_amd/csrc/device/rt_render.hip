@@ -27,6 +27,10 @@
 // camera.h:44-78 and tracer.cpp:291-296): camera_rays_impl, on the frames'
 // jitter draws (jitter_plan_ready / jitter_draws, shared with frame_begin);
 // kernels in rt_camera_f64.hip.  Paper resolve: rt_paper_resolve_device.
+// Node queries (rt_query_node_intersect / rt_query_node_interval,
+// Primitive::intersect / ::interval of one node, geometry.h:62-75): node_impl,
+// on the resident scene plus the node's own program (node_program_resident);
+// kernels in rt_node_kernels.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -58,6 +62,7 @@
 
 using rtamd::kCounterSlots;
 using rtamd::kCounterWords;
+using rtamd::NodeParams;
 using rtamd::PaperParams;
 using rtamd::QueryParams;
 using rtamd::RadianceParams;
@@ -177,6 +182,15 @@ void* jitter_alloc(size_t bytes) {
 }
 void jitter_free(void* p) { (void)hipFree(p); }
 
+// One node's compiled program (compile_node_program) next to the resident
+// scene: built and uploaded by the first query of (node, kind), found there by
+// every later one.  A leaf has no ops (its row reads the node itself).
+struct NodeProg {
+    rtamd::KernelVariant kv;          // pick_node_variant: the row and its namespace
+    std::vector<rtamd::DevOp> host;   // source of the upload (kept alive)
+    DBuf ops;
+};
+
 // Per-device workspace (one render at a time per device; guarded by a mutex).
 struct Workspace {
     std::mutex mu;
@@ -191,6 +205,10 @@ struct Workspace {
     DBuf paper_i, paper_d, paper_aux, fb;
     DBuf q_rays, q_hits, q_mask, q_rgb;       // ray queries from host memory: one chunk's rays / hits / flags / colours
     DBuf q_wo;                                // shading queries from host memory: one chunk's view directions
+    DBuf q_exit;                              // node interval queries from host memory: one chunk's exit records
+    // node queries: the programs of the resident scene's nodes queried so far, by
+    // (node, kind); emptied with the resident scene (release_node_programs)
+    std::map<std::pair<int, int>, NodeProg> node_progs;
     DBuf q_lights;                            // a shading query's own point lights (never the resident scene's `lights`)
     DBuf cam_rows;                            // rt_camera_rays, centre rays: a rows list that is not 0, 1, 2, ...
     rtamd::JitterTable jtab;                  // mt19937(12345) checkpoint table (resident)
@@ -335,6 +353,13 @@ void make_float_scene(SceneCache& f) {
     }
 }
 
+// The node programs belong to the resident scene: they go when it goes.  (No
+// launch reads them then: a call that used one has drained its stream.)
+void release_node_programs(Workspace& ws) {
+    for (auto& kv : ws.node_progs) kv.second.ops.release();
+    ws.node_progs.clear();
+}
+
 // The scene resident in the workspace: compiled and uploaded once (on st), and
 // found there by every later frame or ray query of it on the device.  The
 // caller holds the workspace lock and has reset the staging arena.
@@ -352,6 +377,7 @@ int scene_resident(Workspace& ws, const rt_scene* s, const rt_scene_desc& d, boo
         }
     } add_scene_time{t_sc};
     sc.valid = false;
+    release_node_programs(ws);
     try {
         sc.cs = rtamd::compile_scene(d);
     } catch (const std::exception& e) {
@@ -1170,6 +1196,127 @@ int shade_impl(const char* what, const rt_scene* s, const rt_hit* hits, const do
     return RT_OK;
 }
 
+// ------------------------------------------------------------ node queries
+// The program of (node, kind) of the resident scene d, resident too: compiled
+// (this node's subtree only, so a deep chain's nodes cost their own sizes, not
+// the quadratic sum) and uploaded on st by the first query of it, which counts
+// in rt_setup_times[0] like the scene's own compile; later queries find it.
+// A program deeper than the big stacks is refused here, on the host
+// (pick_node_variant), and leaves no entry.  The caller holds the workspace
+// lock, has reset the staging arena and made the scene resident.
+int node_program_resident(Workspace& ws, const rt_scene_desc& d, int node, int kind, int flags, hipStream_t st,
+                          const NodeProg** out) {
+    const auto key = std::make_pair(node, kind);
+    auto it = ws.node_progs.find(key);
+    if (it != ws.node_progs.end()) {
+        *out = &it->second;
+        return RT_OK;
+    }
+    const auto t_np = SClock::now();
+    struct AddTime {
+        SClock::time_point t;
+        ~AddTime() {
+            std::lock_guard<std::mutex> lk(g_setup.mu);
+            g_setup.scene_ms += ms_since(t);
+        }
+    } add_time{t_np};
+    NodeProg np;
+    try {
+        rtamd::NodeProgram p = rtamd::compile_node_program(d, node, kind);
+        const int rv = rtamd::pick_node_variant(d, node, p, flags, &np.kv);
+        if (rv != RT_OK) return rv;
+        if (np.kv.eager) np.host = std::move(p.ops);
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("node compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+    it = ws.node_progs.emplace(key, std::move(np)).first;
+    if (!it->second.host.empty()) {
+        const hipError_t e = upload(it->second.ops, it->second.host, st, &ws.up);
+        if (e != hipSuccess) {
+            it->second.ops.release();
+            ws.node_progs.erase(it);
+            rtamd::set_last_error(std::string("node program upload failed: ") + hipGetErrorString(e));
+            return RT_ERR_HIP;
+        }
+    }
+    *out = &it->second;
+    return RT_OK;
+}
+
+// rt_query_node_{intersect,interval}[_device]: kind rtamd::kNodeIsect (enter:
+// the hits; ex unused) / kNodeIvl (enter / ex: the enterHit / exitHit records).
+// host: rays and results are host memory, moved through the workspace's chunk
+// buffers (the ray queries' q_rays / q_hits / q_mask, and q_exit); else device
+// memory, evaluated in place on st.
+int node_impl(const char* what, const rt_scene* s, int node, int kind, const rt_ray* rays, size_t n, int flags,
+              rt_hit* enter, rt_hit* ex, uint8_t* mask, bool host, hipStream_t st, rt_stats* stats) {
+    BatchCall call(what, st);
+    const bool isect = kind == rtamd::kNodeIsect;
+    if (!s) return call.fail("scene is NULL", RT_ERR_INVALID_ARG);
+    if (flags & ~kKnownFlags) return call.fail("unknown flag bits", RT_ERR_INVALID_ARG);
+    int rv = rtamd::check_query_flags(flags);
+    if (rv != RT_OK) return rv;
+    const rt_scene_desc& d = *rt_scene_get_desc(s);
+    if (node < 0 || node >= d.n_nodes) return call.fail("node is outside [0, n_nodes)", RT_ERR_INVALID_ARG);
+    call.zero_stats(stats);
+    if (n == 0) return RT_OK;
+    if (!rays) return call.fail("rays is NULL", RT_ERR_INVALID_ARG);
+    if (isect ? !enter : (!enter && !ex && !mask)) return call.fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
+    rv = call.open();
+    if (rv != RT_OK) return rv;
+    Workspace& ws = *call.ws;
+    rv = scene_resident(ws, s, d, false, st);
+    const NodeProg* np = nullptr;
+    if (rv == RT_OK) rv = node_program_resident(ws, d, node, kind, flags, st, &np);
+    if (rv != RT_OK) return rv;
+    SceneView S;
+    scene_view(ws, d, flags, false, S);
+    S.n_chunks = 0;
+    const size_t chunk = host ? std::min(n, g_chunk_items.load()) : n;
+    if (host) {
+        HIP_TRY(ws.q_rays.ensure(chunk * sizeof(rt_ray)));
+        if (enter) HIP_TRY(ws.q_hits.ensure(chunk * sizeof(rt_hit)));
+        if (ex) HIP_TRY(ws.q_exit.ensure(chunk * sizeof(rt_hit)));
+        if (mask) HIP_TRY(ws.q_mask.ensure(chunk));
+    }
+    // a chunk on the device: the staging buffers, or the caller's (one chunk)
+    const rt_ray* d_rays = host ? ws.q_rays.as<rt_ray>() : rays;
+    rt_hit* d_enter = !enter ? nullptr : host ? ws.q_hits.as<rt_hit>() : enter;
+    rt_hit* d_exit = !ex ? nullptr : host ? ws.q_exit.as<rt_hit>() : ex;
+    uint8_t* d_mask = !mask ? nullptr : host ? ws.q_mask.as<uint8_t>() : mask;
+    rv = call.run(
+        n, chunk, kLaunchItems,
+        [&](size_t c0, size_t cn) -> int {
+            if (host) HIP_TRY(hipMemcpyAsync(ws.q_rays.p, rays + c0, cn * sizeof(rt_ray), hipMemcpyHostToDevice, st));
+            return RT_OK;
+        },
+        [&](size_t, size_t l0, size_t ln) -> int {
+            NodeParams P;
+            P.n = ln;
+            P.rays = d_rays + l0;
+            P.enter = d_enter ? d_enter + l0 : nullptr;
+            P.exit = d_exit ? d_exit + l0 : nullptr;
+            P.mask = d_mask ? d_mask + l0 : nullptr;
+            P.ops = np->ops.as<rtamd::DevOp>();
+            P.n_ops = (int)np->host.size();
+            P.node = node;
+            HIP_TRY(rtamd::launch_node(np->kv, kind, st, S, P));
+            return RT_OK;
+        },
+        [&](size_t c0, size_t cn) -> int {
+            if (!host) return RT_OK;
+            if (enter) HIP_TRY(hipMemcpyAsync(enter + c0, d_enter, cn * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+            if (ex) HIP_TRY(hipMemcpyAsync(ex + c0, d_exit, cn * sizeof(rt_hit), hipMemcpyDeviceToHost, st));
+            if (mask) HIP_TRY(hipMemcpyAsync(mask + c0, d_mask, cn, hipMemcpyDeviceToHost, st));
+            return RT_OK;
+        });
+    if (rv == RT_OK) rv = call.finish();
+    if (rv != RT_OK || !stats) return rv;
+    stats->rays_intersect = stats->rays_traced = n;   // (one primitive query per ray)
+    return RT_OK;
+}
+
 // ------------------------------------------------------------- camera rays
 // rt_camera_rays[_device]: the rays of list entries [0, n_rows) of a W x H
 // frame seen through cam (k_camera_rays, rt_camera_f64.hip).  host: rays is
@@ -1381,8 +1528,9 @@ int rtamd::release_device_workspaces(int min_slot) {
                         &w->wobjs, &w->wctab, &w->worig, &w->wchunk,
                         &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->ckpt,
                         &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime,
-                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb, &w->q_wo, &w->q_lights, &w->cam_rows})
+                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb, &w->q_wo, &w->q_exit, &w->q_lights, &w->cam_rows})
             b->release();
+        release_node_programs(*w);
         w->jtab.release();
         w->jcache.release();   // every cached entry and the uncached buffer (the hit / miss counts stay)
         w->counters_zero = false;
@@ -1611,6 +1759,32 @@ extern "C" int rt_query_occluded_device(const rt_scene* s, const rt_ray* rays_de
                                         uint8_t* occluded_dev, void* hip_stream, rt_stats* stats) {
     return query_impl("rt_query_occluded_device", s, rtamd::kQueryOccl, rays_dev, n, flags, nullptr, occluded_dev, nullptr,
                       false, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_query_node_intersect(const rt_scene* s, int node, const rt_ray* rays_host, size_t n, int flags,
+                                       rt_hit* hits_host, uint8_t* hit_mask_host, rt_stats* stats) {
+    return node_impl("rt_query_node_intersect", s, node, rtamd::kNodeIsect, rays_host, n, flags, hits_host, nullptr,
+                     hit_mask_host, true, nullptr, stats);
+}
+
+extern "C" int rt_query_node_interval(const rt_scene* s, int node, const rt_ray* rays_host, size_t n, int flags,
+                                      rt_hit* enter_host, rt_hit* exit_host, uint8_t* ok_mask_host, rt_stats* stats) {
+    return node_impl("rt_query_node_interval", s, node, rtamd::kNodeIvl, rays_host, n, flags, enter_host, exit_host,
+                     ok_mask_host, true, nullptr, stats);
+}
+
+extern "C" int rt_query_node_intersect_device(const rt_scene* s, int node, const rt_ray* rays_dev, size_t n, int flags,
+                                              rt_hit* hits_dev, uint8_t* hit_mask_dev, void* hip_stream,
+                                              rt_stats* stats) {
+    return node_impl("rt_query_node_intersect_device", s, node, rtamd::kNodeIsect, rays_dev, n, flags, hits_dev, nullptr,
+                     hit_mask_dev, false, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_query_node_interval_device(const rt_scene* s, int node, const rt_ray* rays_dev, size_t n, int flags,
+                                             rt_hit* enter_dev, rt_hit* exit_dev, uint8_t* ok_mask_dev, void* hip_stream,
+                                             rt_stats* stats) {
+    return node_impl("rt_query_node_interval_device", s, node, rtamd::kNodeIvl, rays_dev, n, flags, enter_dev, exit_dev,
+                     ok_mask_dev, false, (hipStream_t)hip_stream, stats);
 }
 
 extern "C" int rt_query_radiance(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, double* rgb_host,

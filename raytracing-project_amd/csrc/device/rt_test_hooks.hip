@@ -270,6 +270,52 @@ extern "C" int rt_test_shade_kernel_row(int table, int index, char* out, int cap
     return kernel_row(table ? KernelVariant::kRtdb : KernelVariant::kRtd, &KernelNamespace::shade, index, out, cap);
 }
 
+extern "C" int rt_test_node_kernel_row(int table, int index, char* out, int cap) {
+    if (table != 0 && table != 1) return RT_ERR_INVALID_ARG;
+    return kernel_row(table ? KernelVariant::kRtdb : KernelVariant::kRtd, &KernelNamespace::node, index, out, cap);
+}
+
+extern "C" int rt_test_node_program(const rt_scene* s, int node, int kind, int32_t* ops_out, int cap,
+                                    int32_t* depths_out2) {
+    if (!s || cap < 0 || (cap > 0 && !ops_out)) return RT_ERR_INVALID_ARG;
+    try {
+        const rtamd::NodeProgram p = rtamd::compile_node_program(*rt_scene_get_desc(s), node, kind);
+        for (int i = 0; i < cap && i < (int)p.ops.size(); ++i) {
+            const rtamd::DevOp& o = p.ops[i];
+            const int32_t v[4] = {o.op, o.node, o.top, o.csg_op};
+            std::copy(v, v + 4, ops_out + 4 * (size_t)i);
+        }
+        if (depths_out2) {
+            depths_out2[0] = p.max_ray_depth;
+            depths_out2[1] = p.max_ivl_depth;
+        }
+        return (int)p.ops.size();
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("node compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+}
+
+extern "C" int rt_test_node_kernel_name(const rt_scene* s, int node, int kind, int flags, char* out, int cap) {
+    if (!s || !out || cap <= 0 || (kind != rtamd::kNodeIsect && kind != rtamd::kNodeIvl)) return RT_ERR_INVALID_ARG;
+    KernelVariant v;
+    try {
+        const rt_scene_desc& d = *rt_scene_get_desc(s);
+        const int rc = rtamd::pick_node_variant(d, node, rtamd::compile_node_program(d, node, kind), flags, &v);
+        if (rc != RT_OK) return rc;
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("node compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+    const rtamd::KernelEntry k = kernel_in(rtamd::kernel_namespace(v.ns).node, v, kind);
+    if (!k.name) {
+        rtamd::set_last_error("rt_test_node_kernel_name: no kernel for this variant");
+        return RT_ERR_UNSUPPORTED;
+    }
+    std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
+    return RT_OK;
+}
+
 extern "C" int rt_test_kernel_info(const rt_scene* s, int mode, int flags, int32_t* out) {
     if (!s || !out) return RT_ERR_INVALID_ARG;
     int ndev = 0;

@@ -31,13 +31,13 @@ bool plain_scene(const CompiledScene& cs) {
 
 // Stack tiers: the common kernels, else the big-stack build (rtdb, *big), else
 // refuse.  frames: the reflection / refraction frames the trace needs.
-int stack_tier(const CompiledScene& cs, const rt_scene_desc& d, int frames, bool fp32, bool* big) {
+int stack_tier(int max_ray_depth, int max_ivl_depth, const rt_scene_desc& d, int frames, bool fp32, bool* big) {
     *big = false;
-    if (cs.max_ray_depth > kMaxRayStack || cs.max_ivl_depth > kMaxIvlSpill + 2 || frames > kMaxDepth) {
-        if (cs.max_ray_depth > kBigRayStack || cs.max_ivl_depth > kBigIvlSpill + 2 || frames > kBigDepth) {
+    if (max_ray_depth > kMaxRayStack || max_ivl_depth > kMaxIvlSpill + 2 || frames > kMaxDepth) {
+        if (max_ray_depth > kBigRayStack || max_ivl_depth > kBigIvlSpill + 2 || frames > kBigDepth) {
             set_last_error("scene exceeds the device stacks: transform nesting inside CSG operands " +
-                           std::to_string(cs.max_ray_depth) + " (max " + std::to_string(kBigRayStack) +
-                           "), CSG operand depth " + std::to_string(cs.max_ivl_depth) + " (max " +
+                           std::to_string(max_ray_depth) + " (max " + std::to_string(kBigRayStack) +
+                           "), CSG operand depth " + std::to_string(max_ivl_depth) + " (max " +
                            std::to_string(kBigIvlSpill + 2) + "), medium.recursion " +
                            std::to_string(d.recursion_limit) + " with reflection/refraction (max " +
                            std::to_string(kBigDepth + 1) + ")");
@@ -74,7 +74,8 @@ int pick_common(const CompiledScene& cs, const rt_scene_desc& d, bool frames_if_
         if (d.materials[i].kr > 0.0 || d.materials[i].kt > 0.0) v.secondary = true;
     if (d.recursion_limit < 2) v.secondary = false;   // depth < limit-1 never holds (tracer.cpp:38,51)
     bool big = false;
-    const int rc = stack_tier(cs, d, frames_if_secondary && v.secondary ? d.recursion_limit - 1 : 0, fp32, &big);
+    const int rc = stack_tier(cs.max_ray_depth, cs.max_ivl_depth, d,
+                              frames_if_secondary && v.secondary ? d.recursion_limit - 1 : 0, fp32, &big);
     if (rc != RT_OK) return rc;
     v.ns = big ? KernelVariant::kRtdb : fp32 ? KernelVariant::kRtf : KernelVariant::kRtd;
     // the big-stack build has only the general variants (every feature);
@@ -152,6 +153,26 @@ int pick_radiance_variant(const CompiledScene& cs, const rt_scene_desc& d, int f
     if (rc != RT_OK) return rc;
     if (v.eager) v.secondary = true;   // (the general row: the only eager one)
     v.plain = pick_plain(cs, v);
+    *out = v;
+    return RT_OK;
+}
+
+int pick_node_variant(const rt_scene_desc& d, int node, const NodeProgram& p, int flags, KernelVariant* out) {
+    int rc = check_query_flags(flags);
+    if (rc != RT_OK) return rc;
+    if (node < 0 || node >= d.n_nodes) {
+        set_last_error("node index out of range");
+        return RT_ERR_INVALID_ARG;
+    }
+    KernelVariant v;
+    const int kind = d.nodes[node].kind;
+    if (kind != RT_NODE_SPHERE && kind != RT_NODE_HALFSPACE && kind != RT_NODE_POKEBALL) {
+        bool big = false;
+        rc = stack_tier(p.max_ray_depth, p.max_ivl_depth, d, 0, false, &big);
+        if (rc != RT_OK) return rc;
+        v.ns = big ? KernelVariant::kRtdb : KernelVariant::kRtd;
+        v.eager = true;
+    }
     *out = v;
     return RT_OK;
 }

@@ -90,6 +90,18 @@ int pick_shade_variant(const CompiledScene& cs, const rt_scene_desc& d, int flag
 // refracting hit, and the radiance table has no other eager row.
 int pick_radiance_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
 
+// The variant a node query (rt_query_node_intersect / rt_query_node_interval)
+// of node `node` of d launches, looked up in the node tables (rt_launch.hpp
+// KernelNamespace::node): check_query_flags first; a sphere, half-space or
+// pokeball node takes the leaf row (eager = false: no interpreter, no stacks,
+// namespace rtd whatever the scene); any other node the program row (eager =
+// true) of the stack tier of ITS OWN program p (compile_node_program), not the
+// scene's: rtd within kMaxRayStack / kMaxIvlSpill + 2, rtdb up to kBigRayStack
+// / kBigIvlSpill + 2, beyond that RT_ERR_UNSUPPORTED with the frames' message.
+// The per-lane stacks are fixed arrays, so that refusal is what keeps a deeper
+// program from ever reaching the device.  Only ns and eager are set.
+int pick_node_variant(const rt_scene_desc& d, int node, const NodeProgram& p, int flags, KernelVariant* out);
+
 // ----------------------------------------------------------------- dist plan
 constexpr int kChunks = 4;   // pipeline units per rank (chunk k gathered while k+1 is traced)
 // Paper frames gather one code byte per pixel, so their chunks hide little

@@ -448,6 +448,19 @@ public:
         }
     }
 
+    NodeProgram node_program(int node, int kind) {
+        if (node < 0 || node >= d_.n_nodes) throw std::runtime_error("node index out of range");
+        if (kind != kNodeIsect && kind != kNodeIvl) throw std::runtime_error("unknown node program kind");
+        NodeProgram p;
+        ops_ = &p.ops;
+        rdepth_ = idepth_ = max_r_ = max_i_ = 0;
+        if (kind == kNodeIsect) emit_isect(node, 1, 0);
+        else emit_ivl(node, 0);
+        p.max_ray_depth = max_r_;
+        p.max_ivl_depth = max_i_;
+        return p;
+    }
+
     CompiledScene run() {
         CompiledScene cs;
         ops_ = &cs.ops;
@@ -748,6 +761,11 @@ void pokeball_thresholds(double btn_outer, double ring_width, double& xb, double
 CompiledScene compile_scene(const rt_scene_desc& d) {
     Compiler c(d);
     return c.run();
+}
+
+NodeProgram compile_node_program(const rt_scene_desc& d, int node, int kind) {
+    Compiler c(d);
+    return c.node_program(node, kind);
 }
 
 }  // namespace rtamd

@@ -142,6 +142,24 @@ inline bool accepts_tie(const DevObj& o) {
 // Throws std::runtime_error on malformed IR.
 CompiledScene compile_scene(const rt_scene_desc& d);
 
+// One node's own program (rt_query_node_intersect / rt_query_node_interval):
+// the post-order eager program with full hit records of the subtree under
+// `node` (any node of d.nodes, not only a top-level object's), as an OBJ_EAGER
+// object's is.  kNodeIsect: Primitive::intersect(node, ray, tmin, tmax), the
+// root's ops with top = 1; kNodeIvl: Primitive::interval(node, ray), whose
+// result is the interval stack's top after the last op.  The depths are this
+// program's own (the ray stack and the interval stack it needs), not the
+// scene's: a bare chain of transforms is a stackless OBJ_CHAIN in a frame, but
+// its interval program pushes one ray per transform.  Throws std::runtime_error
+// on malformed IR or a node outside [0, n_nodes).
+enum { kNodeIsect = 0, kNodeIvl = 1 };
+struct NodeProgram {
+    std::vector<DevOp> ops;
+    int max_ray_depth = 0;
+    int max_ivl_depth = 0;
+};
+NodeProgram compile_node_program(const rt_scene_desc& d, int node, int kind);
+
 // Pokeball::pick_region_material (geometry.cpp:163-180) decides its button /
 // ring regions by comparing ang = std::acos(x), x = clamp1(u . btnDir), with
 // btnOuter and inner = max(0, btnOuter - ringWidth).  The host's acos (glibc,

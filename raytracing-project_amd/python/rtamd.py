@@ -201,6 +201,19 @@ def amd_lib():
                                                       C.c_void_p, C.c_void_p, C.POINTER(Stats)]
             lib.rt_query_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                                      C.c_void_p, C.POINTER(Stats)]
+        if hasattr(lib, "rt_query_node_intersect"):   # (absent only in RTAMD_LIB builds of older sources)
+            lib.rt_query_node_intersect.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.POINTER(Stats)]
+            lib.rt_query_node_interval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.rt_query_node_intersect_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.rt_query_node_interval_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.POINTER(Stats)]
+            lib.rt_test_node_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
+            lib.rt_test_node_program.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                                 C.POINTER(C.c_int32)]
         if hasattr(lib, "rt_query_radiance"):   # (absent only in RTAMD_LIB builds of older sources)
             lib.rt_query_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                               C.POINTER(Stats)]
@@ -819,6 +832,114 @@ def query_kernel_name(scene: Scene, kind: int, flags: int = RT_FLAG_NONE) -> tup
     """rt_test_query_kernel_name: (status, "ns::kernel") of the kernel a query
     of kind 0 (intersect) / 1 (occluded) launches.  Host only."""
     return _kernel_name("rt_test_query_kernel_name", scene, kind, flags)
+
+
+# ------------------------------------------------------------- node queries
+NODE_ISECT, NODE_IVL = 0, 1   # node query kinds (scene_compile.hpp kNodeIsect / kNodeIvl)
+
+
+def query_node_intersect(scene: Scene, node: int, origins, dirs, tmin=1e-4, tmax=np.inf, flags: int = RT_FLAG_NONE,
+                         stats: Stats | None = None) -> QueryHits:
+    """rt_query_node_intersect: Primitive::intersect of node `node` (an index
+    into the scene's nodes) for every ray."""
+    rays = make_rays(origins, dirs, tmin, tmax)
+    n = len(rays)
+    hits = np.zeros(n, dtype=HIT_DTYPE)
+    mask = np.zeros(n, dtype=np.uint8)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_node_intersect(scene.handle, node, rays.ctypes.data_as(C.c_void_p), n, flags,
+                                           hits.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p),
+                                           C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return QueryHits(hits, mask.astype(bool))
+
+
+def query_node_interval(scene: Scene, node: int, origins, dirs, flags: int = RT_FLAG_NONE,
+                        stats: Stats | None = None):
+    """rt_query_node_interval: Primitive::interval of node `node` for every
+    ray, as (enter, exit, ok): two rt_hit arrays (HIT_DTYPE; t is tEnter /
+    tExit; zeros with mat -1 where ok is False) and the return values as bools."""
+    rays = make_rays(origins, dirs)
+    n = len(rays)
+    enter, ex = np.zeros(n, dtype=HIT_DTYPE), np.zeros(n, dtype=HIT_DTYPE)
+    mask = np.zeros(n, dtype=np.uint8)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_node_interval(scene.handle, node, rays.ctypes.data_as(C.c_void_p), n, flags,
+                                          enter.ctypes.data_as(C.c_void_p), ex.ctypes.data_as(C.c_void_p),
+                                          mask.ctypes.data_as(C.c_void_p), C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return enter, ex, mask.astype(bool)
+
+
+def query_node_intersect_device(scene: Scene, node: int, rays_dev: DeviceBuffer, n: int, hits_dev: DeviceBuffer,
+                                mask_dev: DeviceBuffer | None, flags: int = RT_FLAG_NONE,
+                                stream: Stream | None = None, stats: Stats | None = None) -> None:
+    """rt_query_node_intersect_device: the first n rt_ray records of rays_dev
+    into the first n rt_hit records of hits_dev (and n flag bytes of mask_dev,
+    when given), on `stream` (None: the default stream)."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize or hits_dev.nbytes < n * HIT_DTYPE.itemsize \
+            or (mask_dev is not None and mask_dev.nbytes < n):
+        raise ValueError("query_node_intersect_device: a buffer is too small for n rays")
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_node_intersect_device(scene.handle, node, rays_dev.ptr, n, flags, hits_dev.ptr,
+                                                  mask_dev.ptr if mask_dev is not None else None,
+                                                  stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def query_node_interval_device(scene: Scene, node: int, rays_dev: DeviceBuffer, n: int,
+                               enter_dev: DeviceBuffer | None, exit_dev: DeviceBuffer | None,
+                               mask_dev: DeviceBuffer | None, flags: int = RT_FLAG_NONE,
+                               stream: Stream | None = None, stats: Stats | None = None) -> None:
+    """rt_query_node_interval_device: the first n rt_ray records of rays_dev
+    into the first n rt_hit records of enter_dev / exit_dev and n flag bytes of
+    mask_dev (each optional, not all three absent), on `stream`."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize \
+            or any(b is not None and b.nbytes < n * HIT_DTYPE.itemsize for b in (enter_dev, exit_dev)) \
+            or (mask_dev is not None and mask_dev.nbytes < n):
+        raise ValueError("query_node_interval_device: a buffer is too small for n rays")
+    st = stats if stats is not None else Stats()
+    ptr = lambda b: b.ptr if b is not None else None   # noqa: E731
+    rc = amd_lib().rt_query_node_interval_device(scene.handle, node, rays_dev.ptr, n, flags, ptr(enter_dev),
+                                                 ptr(exit_dev), ptr(mask_dev), stream.handle if stream else None,
+                                                 C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def node_kernel_name(scene: Scene, node: int, kind: int, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
+    """rt_test_node_kernel_name: (status, "ns::kernel") of the kernel a node
+    query of kind NODE_ISECT / NODE_IVL of this node launches.  Host only."""
+    buf = C.create_string_buffer(160)
+    rc = amd_lib().rt_test_node_kernel_name(scene.handle, node, kind, flags, buf, 160)
+    return rc, buf.value.decode()
+
+
+NODE_TABLES = ("rtd node", "rtdb node")
+
+
+def node_rows(table: int) -> list[str]:
+    """rt_test_node_kernel_row: the rows ("ns::kernel") of node launch table
+    `table` (an index into NODE_TABLES).  Host only."""
+    return _kernel_rows("rt_test_node_kernel_row", table)
+
+
+def node_program(scene: Scene, node: int, kind: int):
+    """rt_test_node_program: (ops, (max_ray_depth, max_ivl_depth)) of the
+    node's own program; ops as (opcode name of OP_CODES, node, top, csg_op)
+    tuples.  Host only."""
+    lib = amd_lib()
+    depths = (C.c_int32 * 2)()
+    n = lib.rt_test_node_program(scene.handle, node, kind, None, 0, depths)
+    if n < 0:
+        raise RTError(n, last_error())
+    buf = (C.c_int32 * (4 * max(1, n)))()
+    assert lib.rt_test_node_program(scene.handle, node, kind, buf, n, depths) == n
+    ops = [(OP_CODES[buf[4 * i]], int(buf[4 * i + 1]), int(buf[4 * i + 2]), int(buf[4 * i + 3])) for i in range(n)]
+    return ops, (int(depths[0]), int(depths[1]))
 
 
 def query_radiance(scene: Scene, origins, dirs, flags: int = RT_FLAG_NONE, stats: Stats | None = None) -> np.ndarray:
@@ -1452,6 +1573,45 @@ def oracle_primary_hits(scene: Scene, W: int | None = None, H: int | None = None
     for f in ("t", "p", "n", "mat", "front_face"):
         rec[f] = hits[f]
     return rec
+
+
+def oracle_node_intersect(scene: Scene, node: int, origins, dirs, tmin=1e-4, tmax=np.inf):
+    """oracle_node_intersect (oracle/oracle.h) ray by ray: (hit flags, rt_hit
+    records; a miss: mat -1 and zeros, as the device reports one)."""
+    rays = make_rays(origins, dirs, tmin, tmax)
+    lib, desc = oracle_lib(), scene.desc_ptr
+    hit = np.zeros(len(rays), dtype=bool)
+    rec = np.zeros(len(rays), dtype=HIT_DTYPE)
+    rec["mat"] = -1
+    h = OracleHit()
+    for k, r in enumerate(rays):
+        o, d = np.ascontiguousarray(r["o"]), np.ascontiguousarray(r["d"])
+        hit[k] = bool(lib.oracle_node_intersect(desc, node, o.ctypes.data_as(_dp), d.ctypes.data_as(_dp),
+                                                float(r["tmin"]), float(r["tmax"]), C.byref(h)))
+        if hit[k]:
+            rec[k] = (h.t, tuple(h.p), tuple(h.n), h.mat, h.front_face)
+    return hit, rec
+
+
+def oracle_node_interval(scene: Scene, node: int, origins, dirs):
+    """oracle_node_interval ray by ray: (enter, exit, ok) as query_node_interval
+    returns them (t = tEnter / tExit, the out-parameters, not the records' own
+    Hit::t; zeros with mat -1 where ok is False)."""
+    rays = make_rays(origins, dirs)
+    lib, desc = oracle_lib(), scene.desc_ptr
+    ok = np.zeros(len(rays), dtype=bool)
+    enter, ex = np.zeros(len(rays), dtype=HIT_DTYPE), np.zeros(len(rays), dtype=HIT_DTYPE)
+    enter["mat"] = ex["mat"] = -1
+    h0, h1 = OracleHit(), OracleHit()
+    t0, t1 = C.c_double(), C.c_double()
+    for k, r in enumerate(rays):
+        o, d = np.ascontiguousarray(r["o"]), np.ascontiguousarray(r["d"])
+        ok[k] = bool(lib.oracle_node_interval(desc, node, o.ctypes.data_as(_dp), d.ctypes.data_as(_dp), C.byref(t0),
+                                              C.byref(t1), C.byref(h0), C.byref(h1)))
+        if ok[k]:
+            enter[k] = (t0.value, tuple(h0.p), tuple(h0.n), h0.mat, h0.front_face)
+            ex[k] = (t1.value, tuple(h1.p), tuple(h1.n), h1.mat, h1.front_face)
+    return enter, ex, ok
 
 
 def oracle_occluded(scene: Scene, origins, dirs, tmin, tmax) -> np.ndarray:

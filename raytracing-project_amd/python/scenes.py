@@ -1733,6 +1733,30 @@ def shade_recipes() -> list[Recipe]:
     return out
 
 
+class NodeRecipe(NamedTuple):
+    """How to launch one row of a node launch table (node_recipes)."""
+    row: str              # "ns::kernel<...>", the table row's own name
+    scene_name: str       # key of recipe_scene()
+    obj: int              # the queried node is top-level object `obj`'s root: desc.objects[obj]
+    kind: int             # 0 rt_query_node_intersect, 1 rt_query_node_interval
+
+
+def node_recipes() -> list[NodeRecipe]:
+    """One NodeRecipe per row of the node launch tables (rt_test.h
+    rt_test_node_kernel_row): k_node_isect<PROG> / k_node_ivl<PROG>.  The leaf
+    rows take a half-space, the program rows of rtd a CSG with transforms
+    inside its operands, those of rtdb the bare chain of 12 transforms (a ray
+    stack of 12) and the right-nested CSG of 12 leaves (an interval stack of
+    12).  tests/test_node_query_plan.py holds this list against the tables,
+    tests/test_gpu_node_query.py queries every entry."""
+    return [NodeRecipe("rtd::k_node_isect<true>", "torture/xform_in_csg", 1, 0),
+            NodeRecipe("rtd::k_node_ivl<true>", "torture/xform_in_csg", 1, 1),
+            NodeRecipe("rtd::k_node_isect<false>", "torture/xform_in_csg", 0, 0),
+            NodeRecipe("rtd::k_node_ivl<false>", "torture/xform_in_csg", 0, 1),
+            NodeRecipe("rtdb::k_node_isect<true>", "deep/xform_nest12", 2, 0),
+            NodeRecipe("rtdb::k_node_ivl<true>", "deep/csg_right12", 1, 1)]
+
+
 def row_timed(row: str, timed: bool) -> str:
     """A paper primary row's name with its T argument set (k_paper_primary<E,
     D, C[, T]>: the untimed rows leave T out; k_paper_primary_lean<C, WV, T,

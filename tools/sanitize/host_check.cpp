@@ -6,8 +6,9 @@
 // (scene_compile.cpp), the frame planners (frame_plan.cpp) and the C oracle,
 // all with -fsanitize=address,undefined; tests/test_sanitize.py runs it over
 // the example, torture and deep scenes plus malformed JSON.  Per scene: load,
-// compile the device object table, pick the frame's kernel variant, render a
-// band of rows on the oracle in both modes, toByte, PNG; then the frame
+// compile the device object table, pick the frame's kernel variant, compile
+// every node's own programs (the node queries') and pick their kernels, render
+// a band of rows on the oracle in both modes, toByte, PNG; then the frame
 // planners over the shapes of tests/test_frame_plan.py and the jitter cache's
 // logic (jitter_cache.cpp) over the scripts of tests/test_jitter_cache.py.
 // Exit 0 = no sanitizer report.
@@ -40,6 +41,15 @@ static int check_file(const char* path, const char* png_out) {
             if (mode == 0) (void)rtamd::pick_radiance_variant(cs, *d, flags, &v);   // (the radiance queries')
             if (mode == 0) (void)rtamd::pick_shade_variant(cs, *d, flags, &v);   // (the shading queries')
         }
+    // every node's own programs and their kernel choice (the node queries': compile_node_program, pick_node_variant)
+    size_t node_ops = 0;
+    for (int node = 0; node < d->n_nodes; ++node)
+        for (int kind : {(int)rtamd::kNodeIsect, (int)rtamd::kNodeIvl}) {
+            const rtamd::NodeProgram p = rtamd::compile_node_program(*d, node, kind);
+            rtamd::KernelVariant v;
+            (void)rtamd::pick_node_variant(*d, node, p, 0, &v);   // (a refusal is a valid outcome)
+            node_ops += p.ops.size();
+        }
     int W = rt_camera_width(&d->camera), H = rt_camera_height(&d->camera);
     if (W > 64) W = 64;
     if (H > 48) H = 48;
@@ -59,7 +69,8 @@ static int check_file(const char* path, const char* png_out) {
             return 1;
         }
     }
-    std::printf("ok %s %dx%d objs=%zu ops=%zu fold=%zu\n", path, W, H, cs.objs.size(), cs.ops.size(), cs.fold.size());
+    std::printf("ok %s %dx%d objs=%zu ops=%zu fold=%zu node_ops=%zu\n", path, W, H, cs.objs.size(), cs.ops.size(),
+                cs.fold.size(), node_ops);
     rt_scene_destroy(s);
     return 0;
 }
