@@ -24,6 +24,7 @@ typedef struct { double t; V3 p; V3 n; int mat; int ff; } Hit;
 typedef struct {
     const rt_scene_desc* s;
     oracle_stats st;
+    int pow_any_x;   /* the caller gives wo (oracle_shade_hits): see spec_pow */
 } Ctx;
 
 static inline double dmax(double a, double b) { return (a < b) ? b : a; } /* std::max(a,b) */
@@ -460,6 +461,46 @@ static int scene_occluded(Ctx* c, const Ray* r, double tmin, double tmax) {
     return 0;
 }
 
+/* ------------------------------------------------------- specular power */
+/* oracle_set_pow: 0 = libm pow (the reference), 1 = the device's split. */
+static int g_pow_mode = 0;
+
+void oracle_set_pow(int mode) { g_pow_mode = mode ? 1 : 0; }
+int oracle_get_pow(void) { return g_pow_mode; }
+
+/* x^k for k >= 1 by left-to-right binary powering in __float128, rounded once
+ * to double.  x holds 53 bits, so x^2 is exact (ties round to even in the
+ * cast) and every later product is within 2^-112: the correctly rounded x^k
+ * unless the exact power lies within ~2^-108 ulp of a rounding boundary. */
+static double pow_int_rounded(double x, int k) {
+    if (k == 0) return 1.0;
+    int top = 0;
+    while ((k >> (top + 1)) != 0) ++top;
+    __float128 q = (__float128)x;
+    for (int i = top - 1; i >= 0; --i) {
+        q = q * q;
+        if ((k >> i) & 1) q = q * (__float128)x;
+    }
+    return (double)q;
+}
+
+/* pow(rdotv, shininess) of shading.cpp:66/120.  Mode 1 answers with the
+ * correctly rounded integer power exactly where the device's pow_spec
+ * (rt_device.hpp) leaves the library's pow: an integer exponent in [0, 1024),
+ * and in the shading queries (RT_POW_ANY_X, any_x here) also |x| <= 2. */
+static double spec_pow_mode(int mode, int any_x, double x, double y) {
+    if (mode == 1 && y >= 0.0 && y < 1024.0 && (double)(int)y == y && (!any_x || fabs(x) <= 2.0))
+        return pow_int_rounded(x, (int)y);
+    return pow(x, y);
+}
+static inline double spec_pow(const Ctx* c, double x, double y) {
+    return spec_pow_mode(g_pow_mode, c->pow_any_x, x, y);
+}
+
+void oracle_spec_pow(int n, const double* x, const double* y, int any_x, double* out) {
+    for (int i = 0; i < n; ++i) out[i] = spec_pow_mode(g_pow_mode, any_x, x[i], y[i]);
+}
+
 /* combine (shading.cpp:6-12) */
 static inline V3 combine(V3 a, V3 b) {
     return v3(1.0 - (1.0 - a.x) * (1.0 - b.x), 1.0 - (1.0 - a.y) * (1.0 - b.y), 1.0 - (1.0 - a.z) * (1.0 - b.z));
@@ -495,7 +536,7 @@ static V3 shade(Ctx* c, const Hit* hit, V3 wo) {
             V3 rr = normalized(v3(2.0 * dot3(n, wi) * n.x - wi.x, 2.0 * dot3(n, wi) * n.y - wi.y,
                                   2.0 * dot3(n, wi) * n.z - wi.z));
             double rdotv = dmax(0.0, dot3(rr, wo));
-            double spec = pow(rdotv, m->shininess) * m->ks;
+            double spec = spec_pow(c, rdotv, m->shininess) * m->ks;
             E_s = v3(L->radiance[0] * spec, L->radiance[1] * spec, L->radiance[2] * spec);
         }
         E_total = combine(E_total, combine(E_d, E_s));
@@ -528,7 +569,7 @@ static V3 shade(Ctx* c, const Hit* hit, V3 wo) {
             V3 rr = normalized(v3(2.0 * dot3(n, wi) * n.x - wi.x, 2.0 * dot3(n, wi) * n.y - wi.y,
                                   2.0 * dot3(n, wi) * n.z - wi.z));
             double rdotv = dmax(0.0, dot3(rr, wo));
-            double spec = pow(rdotv, m->shininess) * m->ks;
+            double spec = spec_pow(c, rdotv, m->shininess) * m->ks;
             E_s = v3(I_L.x * spec, I_L.y * spec, I_L.z * spec);
         }
         V3 E_light = combine(E_d, E_s);
@@ -911,6 +952,25 @@ int oracle_trace_rays(const rt_scene_desc* d, int n, const double* o, const doub
         rgb[3 * i] = col.x; rgb[3 * i + 1] = col.y; rgb[3 * i + 2] = col.z;
         n_isect[i] = c.st.rays_intersect;
         n_occl[i] = c.st.rays_occluded;
+    }
+    return 0;
+}
+
+int oracle_shade_hits(const rt_scene_desc* d, int n, const oracle_hit* hits, const double* wo, const rt_light* lights,
+                       int n_lights, double* rgb, uint64_t* n_occl) {
+    if (!d || n < 0 || (n_lights > 0 && !lights)) return -1;
+    rt_scene_desc sd = *d;
+    if (n_lights >= 0) { sd.lights = lights; sd.n_lights = n_lights; }
+    for (int i = 0; i < n; ++i) {
+        Ctx c; memset(&c, 0, sizeof(c)); c.s = &sd; c.pow_any_x = 1;
+        Hit h = default_hit();
+        h.t = hits[i].t;
+        h.p = vget(hits[i].p);
+        h.n = vget(hits[i].n);
+        h.mat = (hits[i].mat >= 0 && hits[i].mat < sd.n_materials) ? hits[i].mat : -1;
+        V3 col = shade(&c, &h, vget(wo + 3 * i));
+        rgb[3 * i] = col.x; rgb[3 * i + 1] = col.y; rgb[3 * i + 2] = col.z;
+        if (n_occl) n_occl[i] = c.st.rays_occluded;
     }
     return 0;
 }

@@ -65,6 +65,26 @@ int oracle_scene_occluded_batch(const rt_scene_desc* d, int n, const double* o, 
  * that goes through the camera is normalised twice). */
 int oracle_trace_rays(const rt_scene_desc* d, int n, const double* o, const double* dir, double* rgb,
                       uint64_t* n_isect, uint64_t* n_occl);
+/* The specular power, process-wide.  Mode 0 (the default) is libm pow, the
+ * reference: every fixture under tests/golden is bit-equal to it.  Mode 1
+ * returns the correctly rounded x^k from the two pow(rdotv, shininess) calls
+ * of shade() wherever the device takes pow_spec (rt_device.hpp: an integer
+ * exponent in [0, 1024); in oracle_shade_hits, whose wo is the caller's, also
+ * |x| <= 2) and libm everywhere else: the oracle the FP64 kernels are held to
+ * bit for bit (tests/test_gpu_rounding.py).  Set it only between calls. */
+void oracle_set_pow(int mode);
+int oracle_get_pow(void);
+/* out[i] = that power of (x[i], y[i]) in the current mode; any_x as above. */
+void oracle_spec_pow(int n, const double* x, const double* y, int any_x, double* out);
+
+/* shade_lambert_phong(scene, Hit{t, p, n, mat of hits[i]}, wo[3i..]) for n
+ * caller-given hits, the static shade() itself: rgb (3n) and each hit's own
+ * Scene::occluded calls (n_occl, may be NULL).  A mat outside [0, n_materials)
+ * is a null material.  n_lights < 0: the scene's point lights; >= 0: `lights`
+ * instead of them, for this call. */
+int oracle_shade_hits(const rt_scene_desc* d, int n, const oracle_hit* hits, const double* wo, const rt_light* lights,
+                      int n_lights, double* rgb, uint64_t* n_occl);
+
 /* The pixel-centre primary hit of every pixel of the W x H frame, pixel (i, j)
  * at index j*W + i: Camera::generate_ray(i, j) -> dirs, Scene::intersect(r,
  * 1e-4, inf) -> ok, hits. */

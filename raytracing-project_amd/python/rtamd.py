@@ -19,6 +19,7 @@ reference harness (oracle/_ref) are exposed separately for tests only.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -333,8 +334,56 @@ def oracle_lib():
                                           _dp, _dp]
         lib.oracle_jitter.argtypes = [C.c_uint64, C.c_uint64, _dp]
         lib.oracle_mt_words.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
+        if hasattr(lib, "oracle_set_pow"):   # (absent only in a liboracle.so built from older sources: every
+            # earlier entry point stays usable with it; oracle_pow / oracle_shade_hits then raise)
+            lib.oracle_set_pow.argtypes = [C.c_int]
+            lib.oracle_set_pow.restype = None
+            lib.oracle_spec_pow.argtypes = [C.c_int, _dp, _dp, C.c_int, _dp]
+            lib.oracle_spec_pow.restype = None
+            lib.oracle_shade_hits.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, _dp, C.c_void_p, C.c_int, _dp,
+                                              C.c_void_p]
         _oracle = lib
     return _oracle
+
+
+def _oracle_pow_lib():
+    """oracle_lib() with oracle_set_pow, oracle_spec_pow and oracle_shade_hits, or an error that says what to do."""
+    lib = oracle_lib()
+    if not hasattr(lib, "oracle_set_pow"):
+        raise RuntimeError("liboracle.so was built from sources without oracle_set_pow (run __graft_entry__.build())")
+    return lib
+
+
+ORACLE_POW_LIBM = 0     # the reference: libm pow everywhere (every fixture under tests/golden)
+ORACLE_POW_DEVICE = 1   # the correctly rounded x^k wherever the device takes pow_spec (rt_device.hpp)
+
+
+@contextlib.contextmanager
+def oracle_pow(mode: int):
+    """The oracle's specular power (oracle_set_pow, process-wide) for the body
+    of a `with`; mode 0, the reference, is back afterwards whatever happens.
+    Answers computed under mode 1 are the device's yardstick only: keep them
+    out of every cache that mode-0 tests read.  TEST ONLY."""
+    lib = _oracle_pow_lib()
+    if lib.oracle_get_pow() != ORACLE_POW_LIBM:
+        raise RuntimeError("oracle_pow: the oracle is not in mode 0 (a nested or leaked mode)")
+    lib.oracle_set_pow(int(mode))
+    try:
+        yield
+    finally:
+        lib.oracle_set_pow(ORACLE_POW_LIBM)
+
+
+def oracle_spec_pow(x, y, any_x: bool = False) -> np.ndarray:
+    """oracle_spec_pow: the oracle's pow(rdotv, shininess) of (x[i], y[i]) in
+    the current mode (any_x: the shading queries' condition).  TEST ONLY."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    assert x.shape == y.shape and x.ndim == 1
+    out = np.zeros_like(x)
+    _oracle_pow_lib().oracle_spec_pow(len(x), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), 1 if any_x else 0,
+                                 out.ctypes.data_as(_dp))
+    return out
 
 
 def ref_lib():
@@ -1500,6 +1549,32 @@ def oracle_shade(scene: Scene, hits, wo, lights=None):
             E = light_term(lit, E, wi, ndotl, I, 1.5)
         rgb[idx] = np.where(E < 1.5, E, 1.5)   # std::min(1.5, E)
     return rgb, n_occ
+
+
+def oracle_shade_hits(scene: Scene, hits, wo, mask=None, lights=None, miss_rgb=None):
+    """oracle_shade_hits (oracle/oracle.h): the oracle's own shade() of every
+    hit, with query_shade's arguments: (rgb (n, 3), n_occluded (n,)).  Entries
+    with mask 0 are not shaded: miss_rgb (None: the scene's background) and no
+    Scene::occluded call.  What oracle_shade restates in numpy, in the C the
+    frames are held to, so it can judge bits (and follows oracle_pow).  TEST ONLY."""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n = len(hits)
+    w = np.ascontiguousarray(wo, dtype=np.float64)
+    if w.shape != (n, 3):
+        raise ValueError(f"wo must be an (n, 3) array for n = {n} hits, got {w.shape}")
+    arr, nl = _light_array(lights)
+    rgb, no = np.zeros((n, 3)), np.zeros(n, dtype=np.uint64)
+    rc = _oracle_pow_lib().oracle_shade_hits(scene.desc_ptr, n, hits.ctypes.data_as(C.c_void_p), w.ctypes.data_as(_dp),
+                                        C.cast(arr, C.c_void_p) if arr is not None else None, nl,
+                                        rgb.ctypes.data_as(_dp), no.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError("oracle_shade_hits failed")
+    no = no.astype(np.int64)
+    if mask is not None:
+        off = np.asarray(mask).reshape(n) == 0
+        rgb[off] = list(scene.desc.background) if miss_rgb is None else [float(v) for v in miss_rgb]
+        no[off] = 0
+    return rgb, no
 
 
 def oracle_paper_resolve(hits, mask, rgb, W: int, H: int, row0: int, n_rows: int):
