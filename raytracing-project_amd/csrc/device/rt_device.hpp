@@ -60,6 +60,14 @@ __device__ __forceinline__ float sqrt_r(float x) { return __builtin_sqrtf(x); }
 __device__ __forceinline__ float fabs_r(float x) { return __builtin_fabsf(x); }
 
 constexpr real kEPS = RV(1e-6);   // core.h:10
+// CSG::interval's origin-inside test (csg.cpp:98-101: t0 < 1e-6 < t1).  The tracer starts a secondary ray 1e-6
+// off the surface it leaves (tracer.cpp:87-104), and this test has to find the origin on the side that offset
+// chose: inside, the CSG answers with its inside-at-origin hit, outside with its entry hit.  An FP64 hit point
+// is good to 1e-15.  An FP32 one is good to a few 2^-24 |p|, which is 1e-6 at |p| = 7, so with the reference's
+// 1e-6 a third of the rays refracted into a CSG solid started on the wrong side (torture/reflect_refract: the
+// whole solid 0.1 too bright, tests/test_gpu_fp32_bars.py).  The float build tests against 1e-5: above the
+// rounding of a hit point out to |p| = 40, below every offset a shadow ray starts with (1e-3).
+constexpr real kOriginEps = sizeof(real) == sizeof(double) ? RV(1e-6) : RV(1e-5);
 
 #ifdef RT_BIG_STACKS
 constexpr int kMaxDepth = rtamd::kBigDepth;
@@ -515,6 +523,23 @@ __device__ __forceinline__ uint32_t scalar_flag(uint32_t off) {
 }
 
 // --------------------------------------------------------------- primitives
+// The sphere's discriminant (oc.d)^2 - (|oc|^2 - r^2) (geometry.cpp:14-17): in double the reference's own
+// operations.  In float both terms are of size |oc|^2 and their difference of size r^2 at the most, so it
+// comes out with an absolute error of a few 2^-24 |oc|^2 (6e-6 at |oc| = 7): the roots move by that over
+// 2 sqrt(disc), a small sphere's silhouette by that over 2 r, either well beyond the 2^-17 of ray direction
+// that a correct float trace may move a frame by (tests/fp32_bars.py).  The float build takes the same
+// quantity as r^2 - |oc - ((oc.d) / (d.d)) d|^2, the squared distance of the centre from the ray's line:
+// its error is a few 2^-24 |oc| times that distance, which is r at the most.
+__device__ __forceinline__ real sphere_disc(V3 oc, V3 d, real half_b, real cterm, real rad) {
+    if constexpr (sizeof(real) == sizeof(double)) {
+        return half_b * half_b - RV(1.0) * cterm;
+    } else {
+        const real k = half_b / dot3(d, d);
+        const V3 q = v3(oc.x - k * d.x, oc.y - k * d.y, oc.z - k * d.z);
+        return rad * rad - dot3(q, q);
+    }
+}
+
 // Sphere::intersect (geometry.cpp:12-37)
 template <class CT>
 __device__ __forceinline__ bool sphere_intersect(V3 c, real rad, const DRay& ray, real tmin, real tmax,
@@ -523,7 +548,7 @@ __device__ __forceinline__ bool sphere_intersect(V3 c, real rad, const DRay& ray
     V3 oc = v3(ray.o.x - c.x, ray.o.y - c.y, ray.o.z - c.z);
     real half_b = dot3(oc, ray.d);
     real cterm = dot3(oc, oc) - rad * rad;
-    real disc = half_b * half_b - RV(1.0) * cterm;
+    real disc = sphere_disc(oc, ray.d, half_b, cterm, rad);
     if (disc < RV(0.0)) return false;
     real sq = sqrt_r(disc);
     real t = (-half_b - sq) / RV(1.0);
@@ -546,7 +571,7 @@ __device__ __forceinline__ void sphere_interval(V3 c, real r, int mat, const DRa
     V3 oc = v3(ray.o.x - c.x, ray.o.y - c.y, ray.o.z - c.z);
     real half_b = dot3(oc, ray.d);
     real cterm = dot3(oc, oc) - r * r;
-    real disc = half_b * half_b - RV(1.0) * cterm;
+    real disc = sphere_disc(oc, ray.d, half_b, cterm, r);
     o.ok = !(disc < RV(0.0));
     if (!o.ok) return;
     cnt.inc(RT_OPC_SPHERE_IVL_HIT);
@@ -813,8 +838,8 @@ __device__ __forceinline__ void csg_interval(int op, const Ivl& A, const Ivl& B,
             }
         }
     }
-    bool inA = A.ok && (A.t0 < RV(1e-6)) && (A.t1 > RV(1e-6));
-    bool inB = B.ok && (B.t0 < RV(1e-6)) && (B.t1 > RV(1e-6));
+    bool inA = A.ok && (A.t0 < kOriginEps) && (A.t1 > kOriginEps);
+    bool inB = B.ok && (B.t0 < kOriginEps) && (B.t1 > kOriginEps);
     bool inR = csg_combine(op, inA, inB);
     bool haveEnter = false;
     int enterCode = -1, exitCode = -1;
@@ -1034,7 +1059,7 @@ __device__ __forceinline__ void leaf_ivl_c(const NodeT* nd, int pc, const DRay& 
         V3 oc = v3(r.o.x - nd->v[0], r.o.y - nd->v[1], r.o.z - nd->v[2]);
         const real half_b = dot3(oc, r.d);
         const real cterm = dot3(oc, oc) - r0 * r0;
-        const real disc = half_b * half_b - RV(1.0) * cterm;
+        const real disc = sphere_disc(oc, r.d, half_b, cterm, r0);
         o.ok = !(disc < RV(0.0));
         const real s = sqrt_r(o.ok ? disc : RV(0.0));
         real t0 = (-half_b - s) / RV(1.0);
@@ -1072,7 +1097,7 @@ __device__ __forceinline__ void csg_c(int op, const CIvl& A, const CIvl& B, CIvl
         const bool useA = A.ok;
         if (op == RT_CSG_INTERSECTION || (op == RT_CSG_DIFFERENCE && !useA)) return;
         const CIvl& X = useA ? A : B;
-        const bool inX = (X.t0 < RV(1e-6)) && (X.t1 > RV(1e-6));
+        const bool inX = (X.t0 < kOriginEps) && (X.t1 > kOriginEps);
         R.t1 = X.t1;
         R.s1 = X.s1;
         R.c1 = X.c1;
@@ -1108,8 +1133,8 @@ __device__ __forceinline__ void csg_c(int op, const CIvl& A, const CIvl& B, CIvl
                           (fabs_r(A.t1 - B.t1) > e);
         if (easy) {
             cnt.ev(EV_COMB_EASY);
-            const bool inA = (A.t0 < e) && (A.t1 > e);
-            const bool inB = (B.t0 < e) && (B.t1 > e);
+            const bool inA = (A.t0 < kOriginEps) && (A.t1 > kOriginEps);
+            const bool inB = (B.t0 < kOriginEps) && (B.t1 > kOriginEps);
             const bool xa = inA || (!inB && A.t0 < B.t0);
             const real x1 = xa ? A.t1 : B.t1;
             const real y0 = xa ? B.t0 : A.t0;
@@ -1189,8 +1214,8 @@ __device__ __forceinline__ void csg_c(int op, const CIvl& A, const CIvl& B, CIvl
             }
         }
     }
-    bool inA = A.ok && (A.t0 < RV(1e-6)) && (A.t1 > RV(1e-6));
-    bool inB = B.ok && (B.t0 < RV(1e-6)) && (B.t1 > RV(1e-6));
+    bool inA = A.ok && (A.t0 < kOriginEps) && (A.t1 > kOriginEps);
+    bool inB = B.ok && (B.t0 < kOriginEps) && (B.t1 > kOriginEps);
     bool inR = csg_combine(op, inA, inB);
     const bool origin = inR;
     bool haveEnter = inR;
@@ -1384,7 +1409,7 @@ __device__ __forceinline__ void fold_leaf_ivl(const FoldT& L, const DRay& r, CIv
     V3 oc = v3(r.o.x - L.c[0], r.o.y - L.c[1], r.o.z - L.c[2]);
     const real half_b = dot3(oc, r.d);
     const real cterm = dot3(oc, oc) - r0 * r0;
-    const real disc = half_b * half_b - RV(1.0) * cterm;
+    const real disc = sphere_disc(oc, r.d, half_b, cterm, r0);
     o.ok = !(disc < RV(0.0));
     const real sq = sqrt_r(o.ok ? disc : RV(0.0));
     real t0 = (-half_b - sq) / RV(1.0);
@@ -1455,7 +1480,7 @@ __device__ __forceinline__ bool leaf_hit_t(const NodeT* nd, const DRay& r, real 
     V3 oc = v3(r.o.x - nd->v[0], r.o.y - nd->v[1], r.o.z - nd->v[2]);
     const real half_b = dot3(oc, r.d);
     const real cterm = dot3(oc, oc) - rad * rad;
-    const real disc = half_b * half_b - RV(1.0) * cterm;
+    const real disc = sphere_disc(oc, r.d, half_b, cterm, rad);
     if (disc < RV(0.0)) return false;
     const real sq = sqrt_r(disc);
     t = (-half_b - sq) / RV(1.0);

@@ -420,9 +420,21 @@ __device__ __forceinline__ void paper_pixel(const PaperParams& P, int x, int y, 
         P.code[(size_t)ri * P.W + x] = (uint8_t)(eidx | (valid < 4 ? 8 : 0) | (h ? 16 : 0));
         return;
     }
+    double* dst = P.fb + ((size_t)ri * P.W + x) * 3;
+    if constexpr (!std::is_same_v<real, double>) {
+        // The FP32 build decides in float (edge tests, hatch band) but writes the
+        // reference's own FP64 alphabet, as the root of a distributed frame
+        // decodes it: pixel_value<float> gave (float)0.2, (float)0.92, (float)0.94
+        // in an FP64 frame whose stable pixels are otherwise the oracle's.
+        const bool hw = crosshatch(cband, x, y) != RV(0.0);
+        const double v = rtamd::paper_code_value((unsigned)eidx | (valid < 4 ? 8u : 0u) | (hw ? 16u : 0u));
+        dst[0] = v;
+        dst[1] = v;
+        dst[2] = v;
+        return;
+    }
     const real v = rtamd::paper::pixel_value<real>(edge, cband, x, y);
     const V3 o = v3(v, v, v);
-    double* dst = P.fb + ((size_t)ri * P.W + x) * 3;
     dst[0] = o.x;
     dst[1] = o.y;
     dst[2] = o.z;

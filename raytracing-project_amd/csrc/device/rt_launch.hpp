@@ -191,6 +191,10 @@ struct NodeParams {
 // gathers these bytes (1 B/px instead of 24) and the root decodes them with
 // the reference's own FP64 expression, bit for bit.
 __host__ __device__ inline double paper_code_value(unsigned code) {
+    // (every product and difference rounded once, as the reference's: the FP32 kernels' unit contracts, and
+    // fused 1 - 0.2 * 0.4 into 0.92 where the reference has 0.9199999999999999; that unit is compiled with
+    // -ffp-contract=fast-honor-pragmas, since plain fast fuses whatever this pragma says)
+#pragma clang fp contract(off)
     const unsigned i = code & 7;
     double edge = i == 1 ? 0.3 : i == 2 ? 0.5 : i == 3 ? 0.6 : i == 4 ? 0.9 : 0.0;
     if (code & 8) edge *= 0.5;

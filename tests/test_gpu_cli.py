@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fp32_bars as B
 import scenes
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,3 +60,10 @@ def test_cli_fp32_option(gpu, tmp_path):
     ref, _ = gpu.oracle_render(sc, sc.width, sc.height, 0, threads=8)
     d = np.abs(_png(out).astype(int) - gpu.to_rgb8(ref).astype(int))
     assert float(np.mean(d <= 1)) >= 0.99   # non-parity fast path: near, not equal
+    # ... and pixel by pixel: each byte within its pixel's stability bar (tests/fp32_bars.py), one level for
+    # toByte's own rounding, on every pixel the bar constrains
+    _, bar, unconstrained = B.standard_bars(gpu, json.dumps(scene), None, B.seed_of("small/penguin"))
+    over = (d.max(axis=2) > np.ceil(255 * bar) + 1) & ~unconstrained
+    print(f"  ray --fp32 penguin: {over.size} pixels, {float(unconstrained.mean()):.4%} unconstrained, {int(over.sum())} over "
+          f"ceil(255 bar) + 1, largest byte difference on a constrained pixel {int(d.max(axis=2)[~unconstrained].max())}")
+    assert not over.any(), np.argwhere(over)[:6].tolist()
