@@ -183,6 +183,16 @@ int rt_test_normalized(const double* v_host, int n, double* out_host);
  * rdotv at 0).  Returns an rt_status. */
 int rt_test_pow_spec(const double* x_host, const double* y_host, int n, double* out_host);
 
+/* GPU: the specular skip of shade()'s point-light pass 2 (rt_device.hpp
+ * spec_skips, RT_SPEC_SKIP) on caller-given (n, wi, wo, shininess), one lane
+ * per element, launched like rt_test_pow_spec.  With rv = 2 (n.wi) n - wi as
+ * shade() forms it: skip_host[i] = 1 if the trace kernels leave lane i's
+ * specular term out, and plain_host[i] = pow_spec(max(0, normalized(rv) . wo),
+ * shininess), what they compute where they do not.  Tests require plain_host[i]
+ * to be +-0 wherever skip_host[i] is 1.  Returns an rt_status. */
+int rt_test_spec_skip(const double* n_host, const double* wi_host, const double* wo_host, const double* shin_host,
+                      int n, int* skip_host, double* plain_host);
+
 /* Host only: the precomputed mt19937 tree jump polynomials in `path` (the
  * build's lib/mt19937_tree.polys, read by the jitter generator) against the
  * same polynomials computed in this process, first `levels` levels.

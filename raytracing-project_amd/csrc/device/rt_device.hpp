@@ -224,9 +224,23 @@ __device__ __forceinline__ V3 normalized(V3 v) {
     if (r.L > kEPS) return v3(r.q.x, r.q.y, r.q.z);
     return v3(RV(0.0), RV(1.0), RV(0.0));
 }
+// the same with s = dot3(v, v) handed in by a caller that has it already
+__device__ __forceinline__ V3 normalized(V3 v, real s) {
+    const N3 r = sqrt_div3(v.x, v.y, v.z, s);
+    if (r.L > kEPS) return v3(r.q.x, r.q.y, r.q.z);
+    return v3(RV(0.0), RV(1.0), RV(0.0));
+}
 #else
 __device__ __forceinline__ V3 normalized(V3 v) {
     real L = sqrt_r(dot3(v, v));
+    if (L > kEPS) {
+        const auto q = div3(v.x, v.y, v.z, L);
+        return v3(q.x, q.y, q.z);
+    }
+    return v3(RV(0.0), RV(1.0), RV(0.0));
+}
+__device__ __forceinline__ V3 normalized(V3 v, real s) {
+    real L = sqrt_r(s);
     if (L > kEPS) {
         const auto q = div3(v.x, v.y, v.z, L);
         return v3(q.x, q.y, q.z);
@@ -2864,6 +2878,47 @@ __device__ __forceinline__ double pow_spec(double x, double y) {
 }
 __device__ __forceinline__ float pow_spec(float x, float y) { return pow(x, y); }
 
+// RT_SPEC_SKIP=1: shade()'s point-light pass 2 leaves out the specular term
+// (the reflection vector's normalisation, the power and the scaling of Es)
+// in lanes where it is provably +-0: the reflection faces away from the eye.
+// On in the FP64 trace builds, whose wo is the tracer's own normalized(-r.d):
+// a unit vector, the (0, 1, 0) fallback, or NaN.  Off, compiling the previous
+// text, in the float build and in the shading-query builds (RT_POW_ANY_X: a
+// caller-given wo of any length).  RT_SPEC_SKIP=0 is the A/B switch.
+#ifndef RT_SPEC_SKIP
+#define RT_SPEC_SKIP (!RT_POW_ANY_X)
+#endif
+static_assert(!RT_SPEC_SKIP || std::is_same_v<real, double>, "RT_SPEC_SKIP is FP64 only (rt_kernels_f32.hip sets it to 0)");
+
+// True when pow_spec(max(0, dot3(normalized(rv), wo)), shin) is +-0, decided
+// on the unnormalised reflection vector rv with s = dot3(rv, rv) (the sum
+// norm3 starts from), so that the root is not taken either.  The full path
+// computes L = RN(sqrt(s)), q_k = RN(rv_k / L) and d = fl(dot3(q, wo)).  With
+// e = 2^-53, A = sum |rv_k wo_k| <= sqrt(s) |wo| and U the exact sum rv_k wo_k:
+//   q_k = (rv_k / L)(1 + d_k), |d_k| <= e    =>  sum q_k wo_k = (U + e1) / L,  |e1| <= e A
+//   d = sum q_k wo_k + e2,                       |e2| <= 3 e (1 + 2 e) A / L  (two additions, three products)
+//   u = fl(dot3(rv, wo)) = U + e3,               |e3| <= 3 e (1 + e) A
+// so  L d <= u + (1 + 3 + 3) e A (1 + 2 e) < u + 8 e A.  (A product that
+// underflows adds at most 2^-1074 on either side, far inside the factor
+// below.)  The lane skips when
+//   shin = 1 .. 1023   an integer exponent of pow_spec's own loop; pow(x, 0) is
+//                      1 for every x, 0 included, and every other exponent
+//                      stays with the library's pow, whatever it returns
+//   2^-20 <= s <= 4    |rv| <= 2, and L >= 2^-10 is far above kEPS = 1e-6, so
+//                      normalized() does not take its (0, 1, 0) fallback
+//   u <= -2^-40        = 8 e A at A = 2^10: with s <= 4 that covers every
+//                      |wo| <= 512, and the tracer's is 1 (a factor 512)
+// Then d <= 0, max(0, d) is +-0, and pow_spec's products of +-0 are +-0.  A
+// NaN in rv, wo or shin fails a comparison: no skip.  An infinite wo component
+// cannot come out of normalized(); the shading queries, where a caller may
+// hand one in, do not take the skip.  (The exponent's test is loop-invariant
+// in shade(): one lane mask per call.)  tools/probe/spec_skip_check.c runs
+// both evaluations side by side on the host.
+__device__ __forceinline__ bool spec_skips(V3 rv, double s, V3 wo, double shin) {
+    const bool loop = shin > 0.0 && shin < 1024.0 && (double)(int)shin == shin;
+    return loop && s >= 0x1p-20 && s <= 4.0 && dot3(rv, wo) <= -0x1p-40;
+}
+
 // Per-lane LDS pool: shade() keeps pass 1's light geometry (wi, dist) of the
 // first kLightCache lights of each light chunk there for pass 2, instead of
 // recomputing sqrt + three divisions per lit light; flush_counters() reuses
@@ -3063,12 +3118,27 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
             const V3 Ed = v3(alb.x * IL.x * sd, alb.y * IL.y * sd, alb.z * IL.z * sd);
             V3 Es = v3(RV(0.0), RV(0.0), RV(0.0));
             if (ks > RV(0.0)) {
-                cnt.inc(RT_OPC_SHADE_SPEC);
+                cnt.inc(RT_OPC_SHADE_SPEC);   // (the reference's call, skipped below or not)
+#if RT_SPEC_SKIP
+                // A lane whose reflection faces away from the eye keeps Es = +0
+                // (the term's value there is +-0 and combine ignores the sign); a
+                // wave none of whose lit lanes needs the term branches past it.
+                const V3 rv = v3(RV(2.0) * dot3(n, wi) * n.x - wi.x, RV(2.0) * dot3(n, wi) * n.y - wi.y,
+                                 RV(2.0) * dot3(n, wi) * n.z - wi.z);
+                const real s = dot3(rv, rv);
+                if (!spec_skips(rv, s, wo, shin)) {
+                    const V3 rr = normalized(rv, s);
+                    const real rdotv = cmax(RV(0.0), dot3(rr, wo));
+                    const real spec = pow_spec(rdotv, shin) * ks;   // (a -0 here gives Es = -0: combine ignores the sign)
+                    Es = v3(IL.x * spec, IL.y * spec, IL.z * spec);
+                }
+#else
                 const V3 rr = normalized(v3(RV(2.0) * dot3(n, wi) * n.x - wi.x, RV(2.0) * dot3(n, wi) * n.y - wi.y,
                                             RV(2.0) * dot3(n, wi) * n.z - wi.z));
                 const real rdotv = cmax(RV(0.0), dot3(rr, wo));
                 const real spec = pow_spec(rdotv, shin) * ks;   // (a -0 here gives Es = -0: combine ignores the sign)
                 Es = v3(IL.x * spec, IL.y * spec, IL.z * spec);
+#endif
             }
             E = combine(E, combine(Ed, Es));
         }

@@ -6,6 +6,8 @@
 #define RT_NS rtf
 #undef RT_FUSED_NORM
 #define RT_FUSED_NORM 0   // (the fused sqrt + division is FP64 arithmetic: float keeps sqrt_r + div3)
+#undef RT_SPEC_SKIP
+#define RT_SPEC_SKIP 0   // (the specular skip's margin is derived for FP64: float keeps today's text)
 #define RT_NO_PLAIN   // (no plain kernel variants in the FP32 diagnostic build)
 #define RT_NO_PAPER_CODES   // (paper codes are FP64 frames only: no CODES finish kernels)
 #include "rt_device.hpp"

@@ -27,6 +27,21 @@ __global__ void k_test_pow_spec(const double* x, const double* y, int n, double*
     if (i >= n) return;
     out[i] = rtd::pow_spec(x[i], y[i]);
 }
+// spec_skips (rt_device.hpp) on shade()'s own reflection vector, next to the
+// power the lane computes where it does not skip.
+__global__ void k_test_spec_skip(const double* nn, const double* wi, const double* wo, const double* shin, int n,
+                                 int* skip, double* plain) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const rtd::V3 N = rtd::v3(nn[3 * i], nn[3 * i + 1], nn[3 * i + 2]);
+    const rtd::V3 I = rtd::v3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+    const rtd::V3 O = rtd::v3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
+    const rtd::V3 rv = rtd::v3(2.0 * rtd::dot3(N, I) * N.x - I.x, 2.0 * rtd::dot3(N, I) * N.y - I.y,
+                               2.0 * rtd::dot3(N, I) * N.z - I.z);
+    const double s = rtd::dot3(rv, rv);
+    skip[i] = rtd::spec_skips(rv, s, O, shin[i]) ? 1 : 0;
+    plain[i] = rtd::pow_spec(rtd::cmax(0.0, rtd::dot3(rtd::normalized(rv, s), O)), shin[i]);
+}
 // norm3 / normalized (rt_device.hpp) next to __builtin_sqrt and `/` on the
 // same vectors; fast[i]: lane i's wave took the fused path.
 __global__ void k_test_norm3(const double* v, int n, double* oL, double* oq, double* pL, double* pq, int* fast,
@@ -124,6 +139,38 @@ extern "C" int rt_test_pow_spec(const double* x_host, const double* y_host, int 
     if (x) (void)hipFree(x);
     if (y) (void)hipFree(y);
     if (o) (void)hipFree(o);
+    return rc;
+}
+
+extern "C" int rt_test_spec_skip(const double* n_host, const double* wi_host, const double* wo_host,
+                                 const double* shin_host, int n, int* skip_host, double* plain_host) {
+    if (n <= 0 || !n_host || !wi_host || !wo_host || !shin_host || !skip_host || !plain_host) return RT_ERR_INVALID_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RT_ERR_NO_DEVICE;
+    const size_t n1 = (size_t)n * sizeof(double), n3 = 3 * n1, nf = (size_t)n * sizeof(int);
+    double *nn = nullptr, *wi = nullptr, *wo = nullptr, *sh = nullptr, *pl = nullptr;
+    int* sk = nullptr;
+    int rc = RT_OK;
+    if (hipMalloc(&nn, n3) != hipSuccess || hipMalloc(&wi, n3) != hipSuccess || hipMalloc(&wo, n3) != hipSuccess ||
+        hipMalloc(&sh, n1) != hipSuccess || hipMalloc(&pl, n1) != hipSuccess || hipMalloc(&sk, nf) != hipSuccess)
+        rc = RT_ERR_HIP;
+    if (rc == RT_OK && (hipMemcpy(nn, n_host, n3, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(wi, wi_host, n3, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(wo, wo_host, n3, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(sh, shin_host, n1, hipMemcpyHostToDevice) != hipSuccess))
+        rc = RT_ERR_HIP;
+    if (rc == RT_OK) {
+        hipLaunchKernelGGL(k_test_spec_skip, dim3((n + 255) / 256), dim3(256), 0, nullptr, nn, wi, wo, sh, n, sk, pl);
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(skip_host, sk, nf, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(plain_host, pl, n1, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = RT_ERR_HIP;
+    }
+    if (nn) (void)hipFree(nn);
+    if (wi) (void)hipFree(wi);
+    if (wo) (void)hipFree(wo);
+    if (sh) (void)hipFree(sh);
+    if (pl) (void)hipFree(pl);
+    if (sk) (void)hipFree(sk);
     return rc;
 }
 

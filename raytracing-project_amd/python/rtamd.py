@@ -664,6 +664,24 @@ def pow_spec(x, y) -> np.ndarray:
     return out
 
 
+def spec_skip(n, wi, wo, shin) -> tuple[np.ndarray, np.ndarray]:
+    """rt_test_spec_skip: (skip (m,) bool, plain (m,)) of the device's spec_skips
+    (rt_device.hpp) on (n[i], wi[i], wo[i], shin[i]): whether the trace kernels
+    leave the lane's specular term out, and the power they compute where they
+    do not."""
+    lib = amd_lib()
+    _ip = C.POINTER(C.c_int)
+    lib.rt_test_spec_skip.argtypes = [_dp, _dp, _dp, _dp, C.c_int, _ip, _dp]
+    n, wi, wo = (np.ascontiguousarray(a, dtype=np.float64) for a in (n, wi, wo))
+    shin = np.ascontiguousarray(shin, dtype=np.float64)
+    assert n.ndim == 2 and n.shape[1] == 3 and wi.shape == n.shape and wo.shape == n.shape and shin.shape == (len(n),)
+    skip, plain = np.zeros(len(n), dtype=np.int32), np.zeros(len(n))
+    _ok(lib.rt_test_spec_skip(n.ctypes.data_as(_dp), wi.ctypes.data_as(_dp), wo.ctypes.data_as(_dp),
+                              shin.ctypes.data_as(_dp), len(n), skip.ctypes.data_as(_ip), plain.ctypes.data_as(_dp)),
+        "rt_test_spec_skip")
+    return skip.astype(bool), plain
+
+
 _u64p = C.POINTER(C.c_uint64)
 
 

@@ -4,6 +4,7 @@
 # raytracing-project_amd/lib/exp/librtamd_<name>.so (tools/gpu/ab_lib.sh).
 # Usage: tools/build_variant.sh <name> -DFOO=1 ...
 #   e.g. tools/build_variant.sh nofuse -DRT_FUSED_NORM=0   (sqrt_r + div3 at every normalisation)
+#        tools/build_variant.sh noskip -DRT_SPEC_SKIP=0    (every lit light's specular term evaluated)
 set -e
 NAME=$1; shift
 REPO=$(cd "$(dirname "$0")/.." && pwd)
