@@ -38,6 +38,14 @@
  *                               the pixels of a set of rows, raytracer/src/camera.h:44-78
  *   rt_resolve_samples       <- the frame's sample sum and scale
  *                               raytracer/src/tracer.cpp:291-296
+ *   rt_scatter_rays          <- the spawn half of Tracer::trace_recursive: reflect,
+ *                               refract, has_total_internal_reflection, the 1e-6
+ *                               origin offsets and the depth gate, a batch of hits
+ *                               raytracer/src/tracer.cpp:34-67, 76-104
+ *   rt_combine_bounce        <- its unwind half: combine(total, scale(I, k))
+ *                               raytracer/src/tracer.cpp:47, 66, shading.cpp:6-22
+ *   rt_query_radiance_depth  <- Tracer::trace_recursive(r, depth), a batch of rays
+ *                               raytracer/src/tracer.h:46, tracer.cpp:22-73
  *   rt_framebuffer_to_rgb8   <- framebuffer_to_mat_bgr8 / toByte
  *                               raytracer/src/main.cpp:19-34, core.h:313-316
  *   rt_write_png             <- cv::imwrite (main.cpp:86-89)
@@ -81,7 +89,9 @@ extern "C" {
                                rt_rays_wo / rt_rays_wo_device / rt_paper_resolve /
                                rt_paper_resolve_device, and the node queries
                                rt_query_node_intersect / rt_query_node_interval and
-                               their *_device forms) */
+                               their *_device forms, and the bounce-loop links
+                               rt_scatter_rays / rt_combine_bounce /
+                               rt_query_radiance_depth and their *_device forms) */
 
 /* ---------------------------------------------------------------- errors */
 enum rt_status {
@@ -731,6 +741,113 @@ int rt_paper_resolve_device(const rt_hit* hits_dev, const uint8_t* hit_mask_dev,
                             int row0, int n_rows, double* fb_dev, double* edge_dev, void* hip_stream, rt_stats* stats);
 int rt_paper_resolve(const rt_hit* hits_host, const uint8_t* hit_mask_host, const double* rgb_host, int W, int H,
                      int row0, int n_rows, double* fb_host, double* edge_host);
+
+/* ------------------------------------------------ bounce-by-bounce tracing
+ * The recursion of Tracer::trace_recursive (tracer.cpp:22-73) as links of its
+ * own, so that a caller can run it level by level with every buffer on the
+ * device and read, reweight, stop or replace rays between bounces:
+ *   level k:  (hits, mask) = rt_query_intersect(rays_k)
+ *             direct_k     = rt_query_shade(hits, rt_rays_wo(rays_k), mask)   (miss_rgb NULL: the background)
+ *             rays_k+1     = rt_scatter_rays(rays_k, hits, mask, depth = k)   until it spawns nothing
+ *   unwind:   direct_k     = rt_combine_bounce(direct_k, spawn_k, first_k, direct_k+1, w_k+1)  from the last level up
+ * direct_0 is then rt_query_radiance(rays_0) bit for bit, with the same
+ * Scene::intersect / Scene::occluded totals (tests/test_gpu_bounce.py;
+ * rtamd.radiance_bounces_device is this loop).
+ *
+ * rt_scatter_rays: the spawn half (tracer.cpp:34-67) for a batch of parents,
+ * parent i being (rays[i], hits[i]).  r = Ray(rays[i].o, rays[i].d), the
+ * constructor's normalisation as in every query; only d is read, o, tmin and
+ * tmax are NOT READ.  A parent spawns nothing where hit_mask[i] == 0 (a NULL
+ * mask: every entry is a hit), where hits[i].mat == -1, and where hits[i].mat
+ * lies outside [0, n_materials) (a null material, as in rt_query_shade; in the
+ * last two cases no table is read).  can = (int64)depth < (int64)recursion_limit
+ * - 1; any int depth is accepted.  With incident = r.d.normalized() and n, p,
+ * front_face of the hit as stored (n is not normalised):
+ *   reflection, if kr > 0.0 && can:
+ *     direction reflect(incident, n).normalized(), reflect = incident -
+ *     (2.0 * incident.dot(n)) * n; origin front_face ? p + n*1e-6 : p - n*1e-6;
+ *     weight kr
+ *   refraction, if kt > 0.0 && can and there is no total internal reflection:
+ *     eta = front_face ? medium / ri : ri / medium; cos_i = -incident.dot(n);
+ *     sin_t2 = eta*eta*std::max(0.0, 1.0 - cos_i*cos_i); TIR is sin_t2 >= 1.0 (a
+ *     NaN is not TIR, as in the reference); direction (eta*incident + (eta*cos_i -
+ *     sqrt(1.0 - sin_t2))*n).normalized(); origin with the opposite sign of the
+ *     reflection's; weight kt
+ * Every comparison behaves as the reference's does on NaN; normalized() of a
+ * NaN or short vector is (0, 1, 0).
+ * spawn[i] holds the bits RT_SPAWN_REFLECT | RT_SPAWN_REFRACT, first[i] the
+ * number of children of parents 0 .. i-1; the children are compacted in parent
+ * order, a parent's reflection before its refraction, so the same input gives
+ * the same bytes on every run.  Child j is child_rays[j] with weight child_w[j].
+ * A child ray holds the origin and THE DIRECTION HANDED TO THE Ray CONSTRUCTOR
+ * (the .normalized() results above), not the constructor's own result - unlike
+ * rt_camera_rays, which stores what the reference's Ray holds - and tmin = 1e-4,
+ * tmax = +inf.  The query that traces it next builds Ray(o, d) exactly as
+ * tracer.cpp:45 / :64 do; that is what makes the composition equal
+ * rt_query_radiance to the bit (one normalisation more or fewer moves last bits).
+ * *n_children_host (HOST memory in both forms; may not be NULL) always receives
+ * the total m.  m > child_cap is RT_ERR_INVALID_ARG with m written, spawn and
+ * first complete, and nothing written beyond child_cap entries of either child
+ * buffer; child_cap >= 2n can never fail (child_cap == 0 with NULL child
+ * buffers sizes a call).  n == 0 is RT_OK with m = 0 and no launch.  A NULL
+ * scene, n_children_host, or (with n > 0) rays, hits, spawn, first, or a NULL
+ * child buffer with child_cap > 0, or an output that overlaps an input or
+ * another output, is RT_ERR_INVALID_ARG; every argument check comes before any
+ * device work.  There is no flags argument: the call makes no scene query.
+ * stats (may be NULL): every count 0; ms_kernel, ms_total, n_gpus = 1 (the
+ * host form: ms_total only).  The device form uses the current HIP device and
+ * its resident scene copy (the materials, medium index and recursion limit),
+ * which it shares with the frames and queries and leaves as it was: after a
+ * query of the same scene it uploads nothing.  It enqueues on hip_stream (NULL
+ * = the default stream), waits for an open frame of the device and blocks
+ * until done.  One launch takes up to 2^30 parents; a larger n runs as several,
+ * the child index carried across them.  The host form is a plain loop in
+ * librt_host.so over the scene's own rt_scene_desc, compiled without FP
+ * contraction, and needs no device: it is the statement of the rules the
+ * device form matches bit for bit. */
+#define RT_SPAWN_REFLECT 1
+#define RT_SPAWN_REFRACT 2
+int rt_scatter_rays_device(const rt_scene* s, const rt_ray* rays_dev, const rt_hit* hits_dev, const uint8_t* hit_mask_dev,
+                           size_t n, int depth, uint8_t* spawn_dev, uint64_t* first_dev, rt_ray* child_rays_dev,
+                           double* child_w_dev, size_t child_cap, size_t* n_children_host, void* hip_stream,
+                           rt_stats* stats);
+int rt_scatter_rays(const rt_scene* s, const rt_ray* rays_host, const rt_hit* hits_host, const uint8_t* hit_mask_host,
+                    size_t n, int depth, uint8_t* spawn_host, uint64_t* first_host, rt_ray* child_rays_host,
+                    double* child_w_host, size_t child_cap, size_t* n_children_host, rt_stats* stats);
+/* rt_combine_bounce: the unwind half (tracer.cpp:47, :66).  rgb holds 3n
+ * doubles, the parents' direct colours in and their totals out:
+ *   total = rgb[i]
+ *   if spawn[i] & 1: total = combine(total, child_rgb[j] * child_w[j]), j = first[i]
+ *   if spawn[i] & 2: the same with j = first[i] + (spawn[i] & 1)
+ * per channel combine(a, b) = 1.0 - (1.0 - a)*(1.0 - b) and the scale c * w
+ * (shading.cpp:6-22, in that order, no contraction).  A child index >=
+ * n_children is skipped in both forms: a garbage index never reads out of
+ * bounds.  A NULL rgb, spawn or first with n > 0, a NULL child buffer with
+ * n_children > 0, or an rgb that overlaps child_rgb (or another input) is
+ * RT_ERR_INVALID_ARG; n == 0 is RT_OK.  The device form has one lane per
+ * parent, needs no scene and uploads nothing; it runs on hip_stream (NULL = the
+ * default stream) of the current device and blocks until done.  The host form
+ * is a plain loop in librt_host.so and needs no device. */
+int rt_combine_bounce_device(double* rgb_dev, const uint8_t* spawn_dev, const uint64_t* first_dev, size_t n,
+                             const double* child_rgb_dev, const double* child_w_dev, size_t n_children, void* hip_stream);
+int rt_combine_bounce(double* rgb_host, const uint8_t* spawn_host, const uint64_t* first_host, size_t n,
+                      const double* child_rgb_host, const double* child_w_host, size_t n_children);
+/* rt_query_radiance_depth: rt_query_radiance[_device] started at a recursion
+ * depth: rgb[3i .. 3i+2] = Tracer::trace_recursive(Ray(rays[i].o, rays[i].d),
+ * depth) (tracer.h:46).  Every test in trace_recursive compares depth with the
+ * limit only, so this is rt_query_radiance of the same scene with
+ * recursion_limit - depth for its limit (computed in 64 bits, clamped to int):
+ * the same kernels, chosen for that limit, on the resident scene, which is
+ * left alone (a frame or query of s after it uploads nothing and renders as
+ * before).  depth = 0 gives rt_query_radiance's bytes and counts; depth >=
+ * recursion_limit gives black and zero counts; the children of
+ * rt_scatter_rays(depth = k) are traced with depth = k + 1.  Flags, refusals
+ * (a remaining depth beyond the device stacks included) and stats are
+ * rt_query_radiance's. */
+int rt_query_radiance_depth(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, int depth, double* rgb_host,
+                            rt_stats* stats);
+int rt_query_radiance_depth_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, int depth,
+                                   double* rgb_dev, void* hip_stream, rt_stats* stats);
 
 /* ------------------------------------------------------------ host I/O */
 /* toByte(v) = round(clamp01(v)*255) (core.h:316), RGB order. */

@@ -344,6 +344,11 @@ int rt_test_jitter_cache_sim(const int64_t* ops, int n_ops, int64_t budget, int6
  * rt_query_shade.  So that a small frame or batch crosses several chunks.
  * Process-wide; host only. */
 int rt_test_camera_chunk_rays(size_t n);
+/* Parents of one launch group of rt_scatter_rays_device (default and most
+ * 2^30): n from here on, 0: back to the default.  So that a batch of a few
+ * thousand parents crosses several groups and the child index is carried from
+ * one to the next.  Process-wide; host only. */
+int rt_test_scatter_launch_items(size_t n);
 /* GPU: one simulated rank (rank of world) of a distributed frame on the
  * current device through the product's rank path, the RCCL gather replaced by
  * a device copy (rank 0 also places every slot).  Ranks are cached, so a

@@ -3151,6 +3151,38 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
 }
 
 // ---------------------------------------------------------------- tracing
+// The spawn rules of Tracer::trace_recursive (tracer.cpp:38-67), one copy:
+// trace_wave() and trace() below call them per step, the scatter kernels
+// (rt_bounce_f64.hip, rt_scatter_rays) per parent.  `inc` is
+// r.d.normalized() of the traced Ray; n and p are the hit's as stored.  They
+// are functions of values only: the two choices by front_face (eta, and which
+// child starts on which side) stay selects at the call sites, where they always
+// were - moved into a helper they changed the frame kernels' code.
+// reflect(incident, n).normalized() (tracer.cpp:41, 76-78)
+__device__ __forceinline__ V3 reflect_dir(V3 inc, V3 n) {
+    const real k = RV(2.0) * dot3(inc, n);
+    return normalized(v3(inc.x - n.x * k, inc.y - n.y * k, inc.z - n.z * k));
+}
+// cos_i and sin_t2 of has_total_internal_reflection (tracer.cpp:100-104); TIR
+// is sin_t2 >= 1.0 (a NaN is not)
+__device__ __forceinline__ real incident_cos(V3 inc, V3 n) { return -dot3(inc, n); }
+__device__ __forceinline__ real refract_sin_t2(real eta, real cos_i) {
+    return eta * eta * dmax(RV(0.0), RV(1.0) - cos_i * cos_i);
+}
+// refract(incident, n, eta).normalized() where there is no TIR (tracer.cpp:60, 87-98)
+__device__ __forceinline__ V3 refract_dir(V3 inc, V3 n, real eta, real cos_i, real st2) {
+    const real cos_t = sqrt_r(RV(1.0) - st2);
+    const real k = eta * cos_i - cos_t;
+    return normalized(v3(inc.x * eta + n.x * k, inc.y * eta + n.y * k, inc.z * eta + n.z * k));
+}
+// the children's origins (tracer.cpp:44, 63): h.p + h.n * 1e-6 and h.p - h.n * 1e-6
+__device__ __forceinline__ V3 origin_above(const DHit& h) {
+    return v3(h.p.x + h.n.x * RV(1e-6), h.p.y + h.n.y * RV(1e-6), h.p.z + h.n.z * RV(1e-6));
+}
+__device__ __forceinline__ V3 origin_below(const DHit& h) {
+    return v3(h.p.x - h.n.x * RV(1e-6), h.p.y - h.n.y * RV(1e-6), h.p.z - h.n.z * RV(1e-6));
+}
+
 struct Frame {
     V3 total;
     DRay refr;
@@ -3262,16 +3294,12 @@ __device__ __forceinline__ V3 trace_wave(const DevScene& S, DRay r0, uint32_t& n
                 const real eta = h.ff ? (S.medium_index / mat->refractive_index)
                                       : (mat->refractive_index / S.medium_index);
                 const V3 inc = normalized(r.d);
-                const real cos_i = -dot3(inc, h.n);   // tracer.cpp:100-104
-                const real st2 = eta * eta * dmax(RV(0.0), RV(1.0) - cos_i * cos_i);
+                const real cos_i = incident_cos(inc, h.n);   // tracer.cpp:100-104
+                const real st2 = refract_sin_t2(eta, cos_i);
                 if (!(st2 >= RV(1.0))) {
                     want_refr = true;
-                    const real cos_t = sqrt_r(RV(1.0) - st2);   // tracer.cpp:87-98
-                    const real k = eta * cos_i - cos_t;
-                    const V3 rd = normalized(v3(inc.x * eta + h.n.x * k, inc.y * eta + h.n.y * k,
-                                                inc.z * eta + h.n.z * k));
-                    const V3 ro = h.ff ? v3(h.p.x - h.n.x * RV(1e-6), h.p.y - h.n.y * RV(1e-6), h.p.z - h.n.z * RV(1e-6))
-                                       : v3(h.p.x + h.n.x * RV(1e-6), h.p.y + h.n.y * RV(1e-6), h.p.z + h.n.z * RV(1e-6));
+                    const V3 rd = refract_dir(inc, h.n, eta, cos_i, st2);
+                    const V3 ro = h.ff ? origin_below(h) : origin_above(h);
                     refr = make_ray(ro, rd);
                 }
             }
@@ -3282,10 +3310,8 @@ __device__ __forceinline__ V3 trace_wave(const DevScene& S, DRay r0, uint32_t& n
                 cnt.inc(RT_OPC_SECONDARY);
                 if (want_refl) {
                     const V3 inc = normalized(r.d);
-                    const real k = RV(2.0) * dot3(inc, h.n);   // reflect (tracer.cpp:76-78)
-                    const V3 rd = normalized(v3(inc.x - h.n.x * k, inc.y - h.n.y * k, inc.z - h.n.z * k));
-                    const V3 ro = h.ff ? v3(h.p.x + h.n.x * RV(1e-6), h.p.y + h.n.y * RV(1e-6), h.p.z + h.n.z * RV(1e-6))
-                                       : v3(h.p.x - h.n.x * RV(1e-6), h.p.y - h.n.y * RV(1e-6), h.p.z - h.n.z * RV(1e-6));
+                    const V3 rd = reflect_dir(inc, h.n);
+                    const V3 ro = h.ff ? origin_above(h) : origin_below(h);
                     fr.sf = want_refr ? 2 : 0;
                     nxt[2 * sp] = make_ray(ro, rd);
                 } else {
@@ -3414,16 +3440,12 @@ __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect
                         const real eta = h.ff ? (S.medium_index / mat->refractive_index)
                                                 : (mat->refractive_index / S.medium_index);
                         const V3 inc = normalized(r.d);
-                        const real cos_i = -dot3(inc, h.n);   // tracer.cpp:100-104
-                        const real st2 = eta * eta * dmax(RV(0.0), RV(1.0) - cos_i * cos_i);
+                        const real cos_i = incident_cos(inc, h.n);   // tracer.cpp:100-104
+                        const real st2 = refract_sin_t2(eta, cos_i);
                         if (!(st2 >= RV(1.0))) {
                             want_refr = true;
-                            const real cos_t = sqrt_r(RV(1.0) - st2);   // tracer.cpp:87-98
-                            const real k = eta * cos_i - cos_t;
-                            const V3 rd = normalized(v3(inc.x * eta + h.n.x * k, inc.y * eta + h.n.y * k,
-                                                        inc.z * eta + h.n.z * k));
-                            const V3 ro = h.ff ? v3(h.p.x - h.n.x * RV(1e-6), h.p.y - h.n.y * RV(1e-6), h.p.z - h.n.z * RV(1e-6))
-                                               : v3(h.p.x + h.n.x * RV(1e-6), h.p.y + h.n.y * RV(1e-6), h.p.z + h.n.z * RV(1e-6));
+                            const V3 rd = refract_dir(inc, h.n, eta, cos_i, st2);
+                            const V3 ro = h.ff ? origin_below(h) : origin_above(h);
                             refr = make_ray(ro, rd);
                         }
                     }
@@ -3436,10 +3458,8 @@ __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect
                         if (want_refl) {
                             cnt.inc(RT_OPC_SECONDARY);
                             const V3 inc = normalized(r.d);
-                            const real k = RV(2.0) * dot3(inc, h.n);   // reflect (tracer.cpp:76-78)
-                            const V3 rd = normalized(v3(inc.x - h.n.x * k, inc.y - h.n.y * k, inc.z - h.n.z * k));
-                            const V3 ro = h.ff ? v3(h.p.x + h.n.x * RV(1e-6), h.p.y + h.n.y * RV(1e-6), h.p.z + h.n.z * RV(1e-6))
-                                               : v3(h.p.x - h.n.x * RV(1e-6), h.p.y - h.n.y * RV(1e-6), h.p.z - h.n.z * RV(1e-6));
+                            const V3 rd = reflect_dir(inc, h.n);
+                            const V3 ro = h.ff ? origin_above(h) : origin_below(h);
                             f.stage = 0;
                             stk[sp++] = f;
                             r = make_ray(ro, rd);

@@ -31,6 +31,10 @@
 // Primitive::intersect / ::interval of one node, geometry.h:62-75): node_impl,
 // on the resident scene plus the node's own program (node_program_resident);
 // kernels in rt_node_kernels.hpp.
+// Bounce loop (rt_scatter_rays_device / rt_combine_bounce_device, the spawn and
+// the unwind half of Tracer::trace_recursive, tracer.cpp:34-67): scatter_impl on
+// the resident scene's materials; kernels in rt_bounce_f64.hip.
+// rt_query_radiance_depth is query_impl with the remaining depth for its limit.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -52,6 +56,7 @@
 #include "pinned.hpp"
 #include "mt_poly.hpp"
 #include "rt.h"
+#include "rt_bounce.hpp"
 #include "rt_camera.hpp"
 #include "rt_paper.hpp"
 #include "rt_devbuf.hpp"
@@ -211,6 +216,7 @@ struct Workspace {
     std::map<std::pair<int, int>, NodeProg> node_progs;
     DBuf q_lights;                            // a shading query's own point lights (never the resident scene's `lights`)
     DBuf cam_rows;                            // rt_camera_rays, centre rays: a rows list that is not 0, 1, 2, ...
+    DBuf scatter_tmp;                         // rt_scatter_rays_device: a launch group's child total + its scan's words
     rtamd::JitterTable jtab;                  // mt19937(12345) checkpoint table (resident)
     rtamd::JitterJob jjob;
     rtamd::PinnedArena up;                    // page-locked staging of a frame's uploads (pinned.hpp)
@@ -976,12 +982,14 @@ struct BatchCall {
     }
     // s resident in the workspace, the variant `pick` chooses for it, and its
     // view with the flat object list (a batch's items are arbitrary)
+    // (pick_desc: the variant is chosen for that description instead of s's own:
+    // rt_query_radiance_depth's copy with the remaining depth for its limit)
     int scene(const rt_scene* s, int flags,
               int (*pick)(const rtamd::CompiledScene&, const rt_scene_desc&, int, rtamd::KernelVariant*),
-              rtamd::KernelVariant& kv, SceneView& S) {
+              rtamd::KernelVariant& kv, SceneView& S, const rt_scene_desc* pick_desc = nullptr) {
         const rt_scene_desc& d = *rt_scene_get_desc(s);
         int rv = scene_resident(*ws, s, d, false, st);
-        if (rv == RT_OK) rv = pick(ws->sc.cs, d, flags, &kv);
+        if (rv == RT_OK) rv = pick(ws->sc.cs, pick_desc ? *pick_desc : d, flags, &kv);
         if (rv != RT_OK) return rv;
         scene_view(*ws, d, flags, false, S);
         S.n_chunks = 0;
@@ -1045,8 +1053,13 @@ struct BatchCall {
 // doubles per ray).  host: rays and results are host memory, moved through the
 // workspace's chunk buffers; else device memory, traced in place on st.  A
 // radiance query counts its Scene::intersect / Scene::occluded calls.
+// depth (radiance only; null: 0): Tracer::trace_recursive(r, *depth).  Every
+// test there compares depth with the limit only (tracer.cpp:26, 38, 51), so it
+// is the trace of a scene whose limit is recursion_limit - depth: the kernel is
+// picked for that limit (its refusals too) and launched with it in this call's
+// SceneView; the resident scene is what it was.
 int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays, size_t n, int flags, rt_hit* hits,
-               uint8_t* mask, double* rgb, bool host, hipStream_t st, rt_stats* stats) {
+               uint8_t* mask, double* rgb, bool host, hipStream_t st, rt_stats* stats, const int* depth = nullptr) {
     BatchCall call(what, st);
     const bool isect = kind == rtamd::kQueryIsect, radiance = kind == rtamd::kQueryRadiance;
     if (!s) return call.fail("scene is NULL", RT_ERR_INVALID_ARG);
@@ -1059,10 +1072,18 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
     if (radiance ? !rgb : isect ? !hits : !mask) return call.fail("the result buffer is NULL", RT_ERR_INVALID_ARG);
     rtamd::KernelVariant kv;
     SceneView S;
+    rt_scene_desc at_depth = *rt_scene_get_desc(s);
+    if (depth) {
+        const int64_t left = (int64_t)at_depth.recursion_limit - (int64_t)*depth;
+        at_depth.recursion_limit = (int)std::min<int64_t>(std::max<int64_t>(left, INT32_MIN), INT32_MAX);
+    }
     rv = call.open();
-    if (rv == RT_OK) rv = call.scene(s, flags, radiance ? rtamd::pick_radiance_variant : rtamd::pick_query_variant, kv, S);
+    if (rv == RT_OK)
+        rv = call.scene(s, flags, radiance ? rtamd::pick_radiance_variant : rtamd::pick_query_variant, kv, S,
+                        depth ? &at_depth : nullptr);
     if (rv == RT_OK && radiance) rv = call.counters();
     if (rv != RT_OK) return rv;
+    if (depth) S.rec_limit = at_depth.recursion_limit;
     Workspace& ws = *call.ws;
     const size_t chunk = host ? std::min(n, g_chunk_items.load()) : n;
     if (host) {
@@ -1419,10 +1440,84 @@ int camera_rays_impl(const char* what, const rt_camera* cam, int W, int H, int k
     return RT_OK;
 }
 
+// ------------------------------------------------------------- bounce loop
+// Parents of one launch group of rt_scatter_rays_device: kLaunchItems unless
+// rt_test_scatter_launch_items sets another size.
+std::atomic<size_t> g_scatter_items{kLaunchItems};
+
+// rt_scatter_rays_device: the children of n parents (rays[i], hits[i]) at
+// recursion depth `depth`, compacted in parent order (rt_bounce_f64.hip: count,
+// scan, emit per launch group; the group's child total is read back and
+// carried into the next group's first index).  Every buffer is device memory
+// but n_children.  Reads the resident scene's materials, medium index and
+// recursion limit and leaves the resident copy as it was.
+int scatter_impl(const char* what, const rt_scene* s, const rt_ray* rays, const rt_hit* hits, const uint8_t* mask, size_t n,
+                 int depth, uint8_t* spawn, uint64_t* first, rt_ray* child_rays, double* child_w, size_t child_cap,
+                 size_t* n_children, hipStream_t st, rt_stats* stats) {
+    BatchCall call(what, st);
+    int rv = rtamd::scatter_check(what, s, rays, hits, mask, n, spawn, first, child_rays, child_w, child_cap, n_children,
+                                  false);
+    if (rv != RT_OK) return rv;
+    call.zero_stats(stats);
+    *n_children = 0;
+    if (n == 0) return RT_OK;
+    rv = call.open();
+    if (rv != RT_OK) return rv;
+    Workspace& ws = *call.ws;
+    const rt_scene_desc& d = *rt_scene_get_desc(s);
+    rv = scene_resident(ws, s, d, false, st);
+    if (rv != RT_OK) return rv;
+    const size_t group = std::min(std::max<size_t>(g_scatter_items.load(), 1), kLaunchItems);
+    // [0, 8): the group's child total; behind it the scan's words
+    HIP_TRY(ws.scatter_tmp.ensure(8 + rtamd::scatter_count_words(std::min(n, group)) * sizeof(uint32_t)));
+    rtamd::ScatterParams P0{};
+    P0.mats = ws.mats.p;
+    P0.n_mats = d.n_materials;
+    P0.can = rtamd::bounce_can_spawn(depth, d.recursion_limit) ? 1 : 0;
+    P0.medium_index = d.medium_index;
+    P0.child_rays = child_rays;
+    P0.child_w = child_w;
+    P0.child_cap = child_cap;
+    P0.total = ws.scatter_tmp.as<uint64_t>();
+    P0.counts = ws.scatter_tmp.as<uint32_t>() + 2;
+    uint64_t m = 0;
+    rv = call.run(
+        n, n, group, BatchCall::no_staging,
+        [&](size_t, size_t l0, size_t ln) -> int {
+            rtamd::ScatterParams P = P0;
+            P.rays = rays + l0;
+            P.hits = hits + l0;
+            P.mask = mask ? mask + l0 : nullptr;
+            P.n = ln;
+            P.spawn = spawn + l0;
+            P.first = first + l0;
+            P.base = m;
+            HIP_TRY(rtd::launch_scatter(st, P));
+            uint64_t got = 0;
+            HIP_TRY(hipMemcpyAsync(&got, P.total, sizeof(got), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            m += got;
+            return RT_OK;
+        },
+        BatchCall::no_staging);
+    if (rv == RT_OK) rv = call.finish();
+    if (rv != RT_OK) return rv;
+    *n_children = (size_t)m;
+    if (m > child_cap)
+        return call.fail((std::to_string(m) + " children exceed child_cap " + std::to_string(child_cap)).c_str(),
+                         RT_ERR_INVALID_ARG);
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" int rt_test_camera_chunk_rays(size_t n) {
     g_chunk_items.store(n ? n : kChunkItems);
+    return RT_OK;
+}
+
+extern "C" int rt_test_scatter_launch_items(size_t n) {
+    g_scatter_items.store(n ? std::min(n, kLaunchItems) : kLaunchItems);
     return RT_OK;
 }
 
@@ -1528,7 +1623,8 @@ int rtamd::release_device_workspaces(int min_slot) {
                         &w->wobjs, &w->wctab, &w->worig, &w->wchunk,
                         &w->nodes_f, &w->mats_f, &w->lights_f, &w->dlights_f, &w->fold_f, &w->ckpt,
                         &w->jscratch, &w->counters, &w->paper_i, &w->paper_d, &w->paper_aux, &w->fb, &w->gtime,
-                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb, &w->q_wo, &w->q_exit, &w->q_lights, &w->cam_rows})
+                        &w->q_rays, &w->q_hits, &w->q_mask, &w->q_rgb, &w->q_wo, &w->q_exit, &w->q_lights, &w->cam_rows,
+                        &w->scatter_tmp})
             b->release();
         release_node_programs(*w);
         w->jtab.release();
@@ -1797,6 +1893,45 @@ extern "C" int rt_query_radiance_device(const rt_scene* s, const rt_ray* rays_de
                                         void* hip_stream, rt_stats* stats) {
     return query_impl("rt_query_radiance_device", s, rtamd::kQueryRadiance, rays_dev, n, flags, nullptr, nullptr, rgb_dev,
                       false, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_query_radiance_depth(const rt_scene* s, const rt_ray* rays_host, size_t n, int flags, int depth,
+                                       double* rgb_host, rt_stats* stats) {
+    return query_impl("rt_query_radiance_depth", s, rtamd::kQueryRadiance, rays_host, n, flags, nullptr, nullptr, rgb_host,
+                      true, nullptr, stats, &depth);
+}
+
+extern "C" int rt_query_radiance_depth_device(const rt_scene* s, const rt_ray* rays_dev, size_t n, int flags, int depth,
+                                              double* rgb_dev, void* hip_stream, rt_stats* stats) {
+    return query_impl("rt_query_radiance_depth_device", s, rtamd::kQueryRadiance, rays_dev, n, flags, nullptr, nullptr,
+                      rgb_dev, false, (hipStream_t)hip_stream, stats, &depth);
+}
+
+extern "C" int rt_scatter_rays_device(const rt_scene* s, const rt_ray* rays_dev, const rt_hit* hits_dev,
+                                      const uint8_t* hit_mask_dev, size_t n, int depth, uint8_t* spawn_dev,
+                                      uint64_t* first_dev, rt_ray* child_rays_dev, double* child_w_dev, size_t child_cap,
+                                      size_t* n_children_host, void* hip_stream, rt_stats* stats) {
+    return scatter_impl("rt_scatter_rays_device", s, rays_dev, hits_dev, hit_mask_dev, n, depth, spawn_dev, first_dev,
+                        child_rays_dev, child_w_dev, child_cap, n_children_host, (hipStream_t)hip_stream, stats);
+}
+
+extern "C" int rt_combine_bounce_device(double* rgb_dev, const uint8_t* spawn_dev, const uint64_t* first_dev, size_t n,
+                                        const double* child_rgb_dev, const double* child_w_dev, size_t n_children,
+                                        void* hip_stream) {
+    const int rc = rtamd::combine_check("rt_combine_bounce_device", rgb_dev, spawn_dev, first_dev, n, child_rgb_dev,
+                                        child_w_dev, n_children);
+    if (rc != RT_OK || !n) return rc;
+    rtamd::CombineParams P;
+    P.rgb = rgb_dev;
+    P.spawn = spawn_dev;
+    P.first = first_dev;
+    P.n = n;
+    P.child_rgb = child_rgb_dev;
+    P.child_w = child_w_dev;
+    P.n_children = n_children;
+    HIP_TRY(rtd::launch_combine_bounce((hipStream_t)hip_stream, P));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+    return RT_OK;
 }
 
 extern "C" int rt_query_shade(const rt_scene* s, const rt_hit* hits_host, const double* wo_host,

@@ -2,7 +2,9 @@
 // access).  No exceptions cross the ABI: failures return an rt_status and
 // leave the message in rt_last_error().
 #include <atomic>
+#include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <new>
 #include <string>
@@ -165,6 +167,151 @@ extern "C" int rt_paper_resolve(const rt_hit* hits, const uint8_t* mask, const d
                 const double* base = rgb + 3 * ci;
                 const double v = pr::pixel_value<double>(e, pr::hatch_band<double>(pr::luminance<double>(base[0], base[1], base[2])), x, y);
                 fb[3 * oi] = fb[3 * oi + 1] = fb[3 * oi + 2] = v;
+            }
+        }
+    }
+    return RT_OK;
+}
+
+// ------------------------------------------------------------- bounce loop
+// rt_scatter_rays / rt_combine_bounce: the spawn and the unwind half of
+// Tracer::trace_recursive (tracer.cpp:34-67) as plain loops.  Compiled, like
+// the reference, without FMA contraction: the statement of the rules that the
+// device forms (rt_bounce_f64.hip) match bit for bit.
+int rtamd::scatter_check(const char* what, const rt_scene* s, const rt_ray* rays, const rt_hit* hits, const uint8_t* mask,
+                         size_t n, const uint8_t* spawn, const uint64_t* first, const rt_ray* child_rays,
+                         const double* child_w, size_t child_cap, const size_t* n_children, bool n_children_with_buffers) {
+    const auto fail = [what](const char* msg) {
+        set_last_error(std::string(what) + ": " + msg);
+        return (int)RT_ERR_INVALID_ARG;
+    };
+    if (!s) return fail("scene is NULL");
+    if (!n_children) return fail("n_children is NULL");
+    if (!n) return RT_OK;
+    if (!rays || !hits) return fail("rays or hits is NULL");
+    if (!spawn || !first) return fail("spawn or first is NULL");
+    if (child_cap && (!child_rays || !child_w)) return fail("a child buffer is NULL with child_cap > 0");
+    if (n > SIZE_MAX / sizeof(rt_ray)) return fail("n is too large");
+    if (child_cap > SIZE_MAX / sizeof(rt_ray)) return fail("child_cap is too large");
+    const void* ins[3] = {rays, hits, mask};
+    const size_t in_bytes[3] = {n * sizeof(rt_ray), n * sizeof(rt_hit), n};
+    const void* outs[5] = {spawn, first, child_rays, child_w, n_children};
+    const size_t out_bytes[5] = {n, n * sizeof(uint64_t), child_cap * sizeof(rt_ray), child_cap * sizeof(double),
+                                 sizeof(size_t)};
+    for (int o = 0; o < (n_children_with_buffers ? 5 : 4); ++o) {
+        for (int i = 0; i < 3; ++i)
+            if (ranges_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return fail("an output overlaps an input");
+        for (int p = 0; p < o; ++p)
+            if (ranges_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return fail("two outputs overlap");
+    }
+    return RT_OK;
+}
+
+int rtamd::combine_check(const char* what, const double* rgb, const uint8_t* spawn, const uint64_t* first, size_t n,
+                         const double* child_rgb, const double* child_w, size_t n_children) {
+    const auto fail = [what](const char* msg) {
+        set_last_error(std::string(what) + ": " + msg);
+        return (int)RT_ERR_INVALID_ARG;
+    };
+    if (!n) return RT_OK;
+    if (!rgb || !spawn || !first) return fail("NULL buffer");
+    if (n_children && (!child_rgb || !child_w)) return fail("a child buffer is NULL with n_children > 0");
+    if (n > SIZE_MAX / (3 * sizeof(double))) return fail("n is too large");
+    if (n_children > SIZE_MAX / (3 * sizeof(double))) return fail("n_children is too large");
+    if (ranges_overlap(rgb, n * 3 * sizeof(double), child_rgb, n_children * 3 * sizeof(double)))
+        return fail("rgb overlaps child_rgb");
+    if (ranges_overlap(rgb, n * 3 * sizeof(double), child_w, n_children * sizeof(double)) ||
+        ranges_overlap(rgb, n * 3 * sizeof(double), spawn, n) ||
+        ranges_overlap(rgb, n * 3 * sizeof(double), first, n * sizeof(uint64_t)))
+        return fail("rgb overlaps an input");
+    return RT_OK;
+}
+
+extern "C" int rt_scatter_rays(const rt_scene* s, const rt_ray* rays, const rt_hit* hits, const uint8_t* mask, size_t n,
+                               int depth, uint8_t* spawn, uint64_t* first, rt_ray* child_rays, double* child_w,
+                               size_t child_cap, size_t* n_children, rt_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = rtamd::scatter_check("rt_scatter_rays", s, rays, hits, mask, n, spawn, first, child_rays, child_w,
+                                        child_cap, n_children, true);
+    if (rc != RT_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const rt_scene_desc& d = s->d;
+    const bool can = rtamd::bounce_can_spawn(depth, d.recursion_limit);
+    size_t m = 0;
+    const auto emit = [&](const double o[3], const double dir[3], double w) {
+        if (m < child_cap) {
+            rt_ray& c = child_rays[m];
+            for (int k = 0; k < 3; ++k) {
+                c.o[k] = o[k];
+                c.d[k] = dir[k];
+            }
+            c.tmin = 1e-4;
+            c.tmax = HUGE_VAL;
+            child_w[m] = w;
+        }
+        ++m;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        first[i] = m;
+        spawn[i] = 0;
+        if (mask && !mask[i]) continue;
+        const rt_hit& h = hits[i];
+        if (h.mat < 0 || h.mat >= d.n_materials) continue;   // a null material: trace_recursive returns direct
+        const rt_material& mat = d.materials[h.mat];
+        // r = Ray(o, d) (core.h:278), incident = r.d.normalized() (tracer.cpp:40, 57)
+        double rd[3], inc[3];
+        normalized3(rays[i].d, rd);
+        normalized3(rd, inc);
+        const double* nn = h.n;
+        const bool ff = h.front_face != 0;
+        if (mat.kr > 0.0 && can) {
+            const double k = 2.0 * (inc[0] * nn[0] + inc[1] * nn[1] + inc[2] * nn[2]);
+            const double v[3] = {inc[0] - nn[0] * k, inc[1] - nn[1] * k, inc[2] - nn[2] * k};
+            double dir[3], o[3];
+            normalized3(v, dir);
+            for (int c = 0; c < 3; ++c) o[c] = ff ? h.p[c] + nn[c] * 1e-6 : h.p[c] - nn[c] * 1e-6;
+            spawn[i] |= RT_SPAWN_REFLECT;
+            emit(o, dir, mat.kr);
+        }
+        if (mat.kt > 0.0 && can) {
+            const double eta = ff ? (d.medium_index / mat.refractive_index) : (mat.refractive_index / d.medium_index);
+            const double cos_i = -(inc[0] * nn[0] + inc[1] * nn[1] + inc[2] * nn[2]);
+            const double one_m = 1.0 - cos_i * cos_i;
+            const double sin_t2 = eta * eta * (0.0 < one_m ? one_m : 0.0);   // std::max(0.0, .)
+            if (!(sin_t2 >= 1.0)) {
+                const double cos_t = std::sqrt(1.0 - sin_t2);
+                const double k = eta * cos_i - cos_t;
+                const double v[3] = {inc[0] * eta + nn[0] * k, inc[1] * eta + nn[1] * k, inc[2] * eta + nn[2] * k};
+                double dir[3], o[3];
+                normalized3(v, dir);
+                for (int c = 0; c < 3; ++c) o[c] = ff ? h.p[c] - nn[c] * 1e-6 : h.p[c] + nn[c] * 1e-6;
+                spawn[i] |= RT_SPAWN_REFRACT;
+                emit(o, dir, mat.kt);
+            }
+        }
+    }
+    *n_children = m;
+    if (stats) stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (m > child_cap) {
+        set_last_error("rt_scatter_rays: " + std::to_string(m) + " children exceed child_cap " + std::to_string(child_cap));
+        return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
+// combine(total, scale(I, k)) of tracer.cpp:47, 66 (shading.cpp:6-22)
+extern "C" int rt_combine_bounce(double* rgb, const uint8_t* spawn, const uint64_t* first, size_t n,
+                                 const double* child_rgb, const double* child_w, size_t n_children) {
+    const int rc = rtamd::combine_check("rt_combine_bounce", rgb, spawn, first, n, child_rgb, child_w, n_children);
+    if (rc != RT_OK) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        for (int b = 0; b < 2; ++b) {
+            if (!(spawn[i] & (1 << b))) continue;
+            const uint64_t j = first[i] + (b ? (uint64_t)(spawn[i] & 1) : 0);
+            if (j >= n_children) continue;
+            for (int c = 0; c < 3; ++c) {
+                const double e = child_rgb[3 * j + c] * child_w[j];
+                rgb[3 * i + c] = 1.0 - (1.0 - rgb[3 * i + c]) * (1.0 - e);
             }
         }
     }

@@ -23,6 +23,18 @@ uint64_t scene_uid(const rt_scene* s);
 int paper_resolve_check(const char* what, const rt_hit* hits, const uint8_t* mask, const double* rgb, int W, int H,
                         int row0, int n_rows, const double* fb, const double* edge);
 int rays_wo_check(const char* what, const rt_ray* rays, size_t n, const double* wo);
+// The same for rt_scatter_rays[_device] and rt_combine_bounce[_device].
+// scatter_check also covers n == 0 (RT_OK; the caller then reports m = 0).
+// n_children_with_buffers: n_children lies in the buffers' memory (the host
+// form) and may not overlap them; the device form's is host memory beside
+// device buffers, where the comparison means nothing.
+int scatter_check(const char* what, const rt_scene* s, const rt_ray* rays, const rt_hit* hits, const uint8_t* mask, size_t n,
+                  const uint8_t* spawn, const uint64_t* first, const rt_ray* child_rays, const double* child_w,
+                  size_t child_cap, const size_t* n_children, bool n_children_with_buffers);
+int combine_check(const char* what, const double* rgb, const uint8_t* spawn, const uint64_t* first, size_t n,
+                  const double* child_rgb, const double* child_w, size_t n_children);
+// `can` of tracer.cpp:38, 51 for any int depth: depth < recursion_limit - 1 in 64 bits.
+inline bool bounce_can_spawn(int depth, int recursion_limit) { return (int64_t)depth < (int64_t)recursion_limit - 1; }
 // librtamd: free every per-device workspace of slot >= min_slot (rt_shutdown:
 // all of them); returns an rt_status.
 int release_device_workspaces(int min_slot = 0);

@@ -50,6 +50,8 @@ RT_FLAG_FORCE_BVH = 16   # the wave BVH on every frame (no on/off trial frames)
 RT_RAYS_CENTRE = 0     # rt_camera_rays: Camera::generate_ray at the pixel centres
 RT_RAYS_JITTERED = 1   # ... generate_ray_subpixel at the frame's own RT_SPP jitter draws per pixel
 RT_SPP = 8             # samples per pixel of a standard frame (tracer.cpp:283)
+RT_SPAWN_REFLECT = 1   # rt_scatter_rays: the bits of spawn[i]
+RT_SPAWN_REFRACT = 2
 
 NODE_SPHERE, NODE_HALFSPACE, NODE_POKEBALL, NODE_TRANSLATION, NODE_SCALING, NODE_ROTATION, NODE_CSG = range(7)
 CSG_UNION, CSG_INTERSECTION, CSG_DIFFERENCE = range(3)
@@ -171,6 +173,12 @@ def host_lib():
             lib.rt_rays_wo.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
             lib.rt_paper_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_scatter_rays"):   # (likewise)
+            lib.rt_scatter_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t), C.POINTER(Stats)]
+            lib.rt_combine_bounce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_size_t]
         _host = lib
     return _host
 
@@ -237,6 +245,17 @@ def amd_lib():
             lib.rt_rays_wo_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
             lib.rt_paper_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        if hasattr(lib, "rt_scatter_rays_device"):   # (likewise)
+            lib.rt_scatter_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                   C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(Stats)]
+            lib.rt_combine_bounce_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                     C.c_void_p, C.c_size_t, C.c_void_p]
+            lib.rt_query_radiance_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                                    C.POINTER(Stats)]
+            lib.rt_query_radiance_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                           C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.rt_test_scatter_launch_items.argtypes = [C.c_size_t]
         lib.rt_device_count.restype = C.c_int
         lib.rt_render_multi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
                                         C.POINTER(Stats)]
@@ -1287,6 +1306,219 @@ def paper_resolve_device(hits_dev: DeviceBuffer, mask_dev: DeviceBuffer | None, 
         raise RTError(rc, last_error())
 
 
+def scatter_rays(scene: Scene, rays, hits, mask=None, depth: int = 0, child_cap: int | None = None,
+                 stats: Stats | None = None):
+    """rt_scatter_rays (host): the children that Tracer::trace_recursive spawns
+    at recursion depth `depth` for the parents (rays[i], hits[i]) (RAY_DTYPE /
+    HIT_DTYPE arrays; mask: n bytes or None = every entry is a hit).  Returns
+    (spawn (n,) uint8, first (n,) uint64, child_rays (m,) RAY_DTYPE, child_w
+    (m,)), compacted in parent order, reflection before refraction.  child_cap
+    (None: 2n, which cannot fail): with fewer than m entries the call raises
+    RTError with the needed m in `.needed`."""
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n = len(rays)
+    if hits.shape != (n,):
+        raise ValueError(f"hits must hold n = {n} records, got {hits.shape}")
+    m_in = None
+    if mask is not None:
+        m_in = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m_in.shape != (n,):
+            raise ValueError(f"mask must hold n = {n} flags, got {m_in.shape}")
+    cap = 2 * n if child_cap is None else int(child_cap)
+    spawn, first = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint64)
+    child_rays, child_w = np.zeros(cap, dtype=RAY_DTYPE), np.zeros(cap, dtype=np.float64)
+    m = C.c_size_t(0)
+    st = stats if stats is not None else Stats()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    rc = host_lib().rt_scatter_rays(scene.handle, ptr(rays), ptr(hits), ptr(m_in) if m_in is not None else None, n,
+                                    depth, ptr(spawn), ptr(first), ptr(child_rays), ptr(child_w), cap, C.byref(m),
+                                    C.byref(st))
+    if rc != RT_OK:
+        err = RTError(rc, last_error())
+        err.needed = int(m.value)
+        raise err
+    return spawn, first, child_rays[:m.value], child_w[:m.value]
+
+
+def scatter_rays_device(scene: Scene, rays_dev: DeviceBuffer, hits_dev: DeviceBuffer, mask_dev: DeviceBuffer | None,
+                        n: int, depth: int, spawn_dev: DeviceBuffer, first_dev: DeviceBuffer,
+                        child_rays_dev: DeviceBuffer | None, child_w_dev: DeviceBuffer | None, child_cap: int,
+                        stream: Stream | None = None, stats: Stats | None = None) -> int:
+    """rt_scatter_rays_device: the same from the first n records of rays_dev /
+    hits_dev (and n bytes of mask_dev, when given) into spawn_dev (n bytes),
+    first_dev (n uint64) and at most child_cap records of child_rays_dev /
+    doubles of child_w_dev, on `stream`.  Returns m, the number of children;
+    m > child_cap raises RTError with m in `.needed`."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize or hits_dev.nbytes < n * HIT_DTYPE.itemsize \
+            or (mask_dev is not None and mask_dev.nbytes < n) or spawn_dev.nbytes < n or first_dev.nbytes < 8 * n \
+            or child_cap < 0 or (child_cap and (child_rays_dev is None or child_w_dev is None)) \
+            or (child_rays_dev is not None and child_rays_dev.nbytes < child_cap * RAY_DTYPE.itemsize) \
+            or (child_w_dev is not None and child_w_dev.nbytes < child_cap * 8):
+        raise ValueError("scatter_rays_device: a buffer is too small")
+    m = C.c_size_t(0)
+    st = stats if stats is not None else Stats()
+    opt = lambda b: b.ptr if b is not None else None   # noqa: E731
+    rc = amd_lib().rt_scatter_rays_device(scene.handle, rays_dev.ptr, hits_dev.ptr, opt(mask_dev), n, depth,
+                                          spawn_dev.ptr, first_dev.ptr, opt(child_rays_dev), opt(child_w_dev), child_cap,
+                                          C.byref(m), stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        err = RTError(rc, last_error())
+        err.needed = int(m.value)
+        raise err
+    return int(m.value)
+
+
+def combine_bounce(rgb, spawn, first, child_rgb, child_w) -> np.ndarray:
+    """rt_combine_bounce (host): the parents' direct colours rgb (n, 3) folded
+    with their children's colours child_rgb (m, 3) scaled by child_w (m,), as
+    tracer.cpp:47, :66 do; returns the totals (n, 3) (rgb is not changed)."""
+    out = np.array(rgb, dtype=np.float64, order="C", copy=True)
+    n = out.size // 3
+    spawn = np.ascontiguousarray(spawn, dtype=np.uint8)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    crgb = np.ascontiguousarray(child_rgb, dtype=np.float64)
+    cw = np.ascontiguousarray(child_w, dtype=np.float64)
+    if out.size != 3 * n or spawn.size != n or first.size != n or crgb.size != 3 * cw.size:
+        raise ValueError("combine_bounce: rgb (n, 3), spawn (n,), first (n,), child_rgb (m, 3), child_w (m,)")
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None   # noqa: E731
+    rc = host_lib().rt_combine_bounce(ptr(out), ptr(spawn), ptr(first), n, ptr(crgb), ptr(cw), cw.size)
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return out
+
+
+def combine_bounce_device(rgb_dev: DeviceBuffer, spawn_dev: DeviceBuffer, first_dev: DeviceBuffer, n: int,
+                          child_rgb_dev: DeviceBuffer | None, child_w_dev: DeviceBuffer | None, n_children: int,
+                          stream: Stream | None = None) -> None:
+    """rt_combine_bounce_device: the same in place on the first 3n doubles of
+    rgb_dev, on `stream`."""
+    if n < 0 or rgb_dev.nbytes < 24 * n or spawn_dev.nbytes < n or first_dev.nbytes < 8 * n or n_children < 0 \
+            or (n_children and (child_rgb_dev is None or child_w_dev is None)) \
+            or (child_rgb_dev is not None and child_rgb_dev.nbytes < 24 * n_children) \
+            or (child_w_dev is not None and child_w_dev.nbytes < 8 * n_children):
+        raise ValueError("combine_bounce_device: a buffer is too small")
+    opt = lambda b: b.ptr if b is not None else None   # noqa: E731
+    rc = amd_lib().rt_combine_bounce_device(rgb_dev.ptr, spawn_dev.ptr, first_dev.ptr, n, opt(child_rgb_dev),
+                                            opt(child_w_dev), n_children, stream.handle if stream else None)
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def query_radiance_depth(scene: Scene, origins, dirs, depth: int, flags: int = RT_FLAG_NONE,
+                         stats: Stats | None = None) -> np.ndarray:
+    """rt_query_radiance_depth: Tracer::trace_recursive(Ray(o, d), depth) of
+    every ray, as an (n, 3) float64 array."""
+    rays = make_rays(origins, dirs)
+    n = len(rays)
+    rgb = np.zeros((n, 3), dtype=np.float64)
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_radiance_depth(scene.handle, rays.ctypes.data_as(C.c_void_p), n, flags, depth,
+                                           rgb.ctypes.data_as(C.c_void_p), C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return rgb
+
+
+def query_radiance_depth_device(scene: Scene, rays_dev: DeviceBuffer, n: int, depth: int, rgb_dev: DeviceBuffer,
+                                flags: int = RT_FLAG_NONE, stream: Stream | None = None,
+                                stats: Stats | None = None) -> None:
+    """rt_query_radiance_depth_device: the first n rt_ray records of rays_dev
+    into the first 3n doubles of rgb_dev, started at recursion depth `depth`."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize or rgb_dev.nbytes < n * 24:
+        raise ValueError("query_radiance_depth_device: a buffer is too small for n rays")
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_radiance_depth_device(scene.handle, rays_dev.ptr, n, flags, depth, rgb_dev.ptr,
+                                                  stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
+def scatter_launch_items(n: int) -> None:
+    """rt_test_scatter_launch_items: parents per launch group of
+    scatter_rays_device (0: the default, 2^30)."""
+    _ok(amd_lib().rt_test_scatter_launch_items(n), "rt_test_scatter_launch_items")
+
+
+def radiance_bounces_device(scene: Scene, rays_dev: DeviceBuffer, n: int, flags: int = RT_FLAG_NONE,
+                            stream: Stream | None = None, per_level: list | None = None):
+    """Tracer::trace of the first n rays of rays_dev as the bounce loop, every
+    buffer on the device: per level k query_intersect_device -> rays_wo_device
+    -> query_shade_device (the hit mask, miss_rgb None: the background), then
+    scatter_rays_device(depth = k) until it spawns nothing, then
+    combine_bounce_device from the last level up.  Returns (rgb_dev, the level
+    sizes, the summed Stats); the colours equal query_radiance_device's bit for
+    bit and the ray counts are its counts.  recursion_limit <= 0: all black
+    without a launch.  per_level (optional list): one dict per level with its
+    size and each call's ms_kernel / ms_total is appended, and one for the
+    unwind."""
+    total = Stats()
+    total.n_gpus = 1
+    rgb0 = DeviceBuffer(max(24 * n, 16))   # (zero-filled)
+    if n <= 0 or scene.desc.recursion_limit <= 0:
+        return rgb0, [], total
+
+    def add(st: Stats, rec: dict | None, name: str):
+        total.rays_intersect += st.rays_intersect
+        total.rays_occluded += st.rays_occluded
+        total.rays_traced += st.rays_traced
+        total.ms_kernel += st.ms_kernel
+        total.ms_total += st.ms_total
+        if rec is not None:
+            rec[name] = {"ms_kernel": st.ms_kernel, "ms_total": st.ms_total}
+
+    import time
+    levels = []   # (n, rgb, spawn, first, child_w, m)
+    cur, cur_n, rgb, depth = rays_dev, n, rgb0, 0
+    while True:
+        rec = {"level": depth, "n": cur_n} if per_level is not None else None
+        hits, mask, wo = DeviceBuffer(64 * cur_n), DeviceBuffer(max(cur_n, 16)), DeviceBuffer(24 * cur_n)
+        st = Stats()
+        query_intersect_device(scene, cur, cur_n, hits, mask, flags, stream, st)
+        add(st, rec, "intersect")
+        t0 = time.perf_counter()
+        rays_wo_device(cur, cur_n, wo, stream)
+        if rec is not None:
+            rec["rays_wo"] = {"ms_total": (time.perf_counter() - t0) * 1e3}
+        st = Stats()
+        query_shade_device(scene, hits, wo, mask, cur_n, rgb, None, None, flags, stream, st)
+        add(st, rec, "shade")
+        wo.free()
+        spawn, first = DeviceBuffer(max(cur_n, 16)), DeviceBuffer(8 * cur_n)
+        child_rays, child_w = DeviceBuffer(128 * cur_n), DeviceBuffer(16 * cur_n)
+        st = Stats()
+        m = scatter_rays_device(scene, cur, hits, mask, cur_n, depth, spawn, first, child_rays, child_w, 2 * cur_n, stream,
+                                st)
+        add(st, rec, "scatter")
+        hits.free()
+        mask.free()
+        if rec is not None:
+            rec["children"] = m
+            per_level.append(rec)
+        levels.append((cur_n, rgb, spawn, first, child_w, m))
+        if cur is not rays_dev:
+            cur.free()
+        if m == 0:
+            child_rays.free()
+            break
+        cur, cur_n, depth = child_rays, m, depth + 1
+        rgb = DeviceBuffer(24 * cur_n)
+    t0 = time.perf_counter()
+    for k in range(len(levels) - 2, -1, -1):
+        ln, lrgb, spawn, first, child_w, m = levels[k]
+        combine_bounce_device(lrgb, spawn, first, ln, levels[k + 1][1], child_w, m, stream)
+    dt = (time.perf_counter() - t0) * 1e3
+    total.ms_total += dt
+    if per_level is not None:
+        per_level.append({"unwind": {"ms_total": dt}})
+    for k, lv in enumerate(levels):
+        for b in lv[2:5]:
+            b.free()
+        if k:
+            lv[1].free()
+    return rgb0, [lv[0] for lv in levels], total
+
+
 def camera_chunk_rays(n: int) -> None:
     """rt_test_camera_chunk_rays: items per staging chunk of the batched calls'
     host forms - rays of camera_rays (whole rows, at least one), rays of
@@ -1645,6 +1877,128 @@ def oracle_paper_resolve(hits, mask, rgb, W: int, H: int, row0: int, n_rows: int
         out = np.where(edge > 0.3, hatch * (1.0 - (edge - 0.3) * 0.4), hatch)
         out = np.where(edge > 0.8, 0.0, np.where(edge > 0.5, 0.2, out))
     return np.repeat(out[..., None], 3, axis=2), edge
+
+
+def oracle_scatter(scene: Scene, rays, hits, mask=None, depth: int = 0):
+    """scatter_rays' result from a vectorised numpy restatement of the spawn
+    half of Tracer::trace_recursive (tracer.cpp:34-67, reflect / refract /
+    has_total_internal_reflection :76-104, Ray::Ray and Dir3::normalized of
+    core.h), statement by statement in float64: (spawn, first, child_rays,
+    child_w).  std::max(0.0, x) is x if 0.0 < x else 0.0.  TEST ONLY."""
+    rays = np.asarray(rays, dtype=RAY_DTYPE)
+    hits = np.asarray(hits, dtype=HIT_DTYPE)
+    n = len(rays)
+    d = scene.desc
+    nm = int(d.n_materials)
+    mats = np.array([[d.materials[i].kr, d.materials[i].kt, d.materials[i].refractive_index] for i in range(nm)],
+                    dtype=np.float64).reshape(nm, 3)
+    on = np.ones(n, dtype=bool) if mask is None else np.asarray(mask).reshape(n) != 0
+    mat = hits["mat"].astype(np.int64)
+    on &= (mat >= 0) & (mat < nm)
+    mi = np.where(on, mat, 0)
+    if nm:
+        kr, kt, ri = mats[mi, 0], mats[mi, 1], mats[mi, 2]
+    else:
+        kr = kt = ri = np.zeros(n)
+    can = int(depth) < int(d.recursion_limit) - 1
+    medium = float(d.medium_index)
+
+    def normalized(v):   # core.h:95-101
+        L = np.sqrt(v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1] + v[:, 2] * v[:, 2])
+        return np.where((L > 1e-6)[:, None], v / L[:, None], np.array([0.0, 1.0, 0.0]))
+
+    with np.errstate(all="ignore"):
+        rd = normalized(rays["d"].astype(np.float64))   # Ray::Ray (core.h:278)
+        inc = normalized(rd)                       # r.d.normalized()
+        nn, p, ff = hits["n"], hits["p"], hits["front_face"] != 0
+        idn = inc[:, 0] * nn[:, 0] + inc[:, 1] * nn[:, 1] + inc[:, 2] * nn[:, 2]
+        refl = on & (kr > 0.0) & can
+        k = 2.0 * idn
+        refl_dir = normalized(inc - nn * k[:, None])
+        above, below = p + nn * 1e-6, p - nn * 1e-6
+        refl_o = np.where(ff[:, None], above, below)
+        eta = np.where(ff, medium / ri, ri / medium)
+        cos_i = -idn
+        one_m = 1.0 - cos_i * cos_i
+        sin_t2 = eta * eta * np.where(0.0 < one_m, one_m, 0.0)
+        tir = sin_t2 >= 1.0
+        refr = on & (kt > 0.0) & can & ~tir
+        cos_t = np.sqrt(1.0 - sin_t2)
+        kk = eta * cos_i - cos_t
+        refr_dir = normalized(inc * eta[:, None] + nn * kk[:, None])
+        refr_o = np.where(ff[:, None], below, above)
+    spawn = (refl * RT_SPAWN_REFLECT + refr * RT_SPAWN_REFRACT).astype(np.uint8)
+    cnt = refl.astype(np.uint64) + refr.astype(np.uint64)
+    first = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.uint64) if n else np.zeros(0, dtype=np.uint64)
+    m = int(cnt.sum())
+    child = np.zeros(m, dtype=RAY_DTYPE)
+    w = np.zeros(m)
+    child["tmin"], child["tmax"] = 1e-4, np.inf
+    j1 = first[refl].astype(np.int64)
+    child["o"][j1], child["d"][j1], w[j1] = refl_o[refl], refl_dir[refl], kr[refl]
+    j2 = (first[refr] + refl[refr]).astype(np.int64)
+    child["o"][j2], child["d"][j2], w[j2] = refr_o[refr], refr_dir[refr], kt[refr]
+    return spawn, first, child, w
+
+
+def oracle_combine_bounce(rgb, spawn, first, child_rgb, child_w) -> np.ndarray:
+    """combine_bounce's result from a numpy restatement of tracer.cpp:47, :66
+    with combine and scale of shading.cpp:6-22: per channel 1.0 - (1.0 - a) *
+    (1.0 - c * w); a child index past the children is skipped.  TEST ONLY."""
+    out = np.array(rgb, dtype=np.float64, copy=True).reshape(-1, 3)
+    spawn = np.asarray(spawn, dtype=np.uint8)
+    first = np.asarray(first, dtype=np.uint64)
+    crgb = np.asarray(child_rgb, dtype=np.float64).reshape(-1, 3)
+    cw = np.asarray(child_w, dtype=np.float64).reshape(-1)
+    m = len(cw)
+    with np.errstate(all="ignore"):
+        for bit in (1, 2):
+            j = first + (spawn & 1).astype(np.uint64) if bit == 2 else first   # (wraps mod 2^64, as the C does)
+            sel = ((spawn & bit) != 0) & (j < np.uint64(m))
+            js = j[sel].astype(np.int64)
+            e = crgb[js] * cw[js][:, None]
+            out[sel] = 1.0 - (1.0 - out[sel]) * (1.0 - e)
+    return out
+
+
+def oracle_radiance_bounces(scene: Scene, rays, scatter=None, combine=None, peel_first: bool = False):
+    """Tracer::trace of an rt_ray array as the bounce loop on the CPU: per
+    level oracle_scene_intersect -> rays_wo -> oracle_shade_hits, then
+    `scatter` (default: the host form scatter_rays; signature (scene, rays,
+    hits, mask, depth)), then `combine` (default: combine_bounce) from the last
+    level up.  Returns (rgb (n, 3), level sizes, Scene::intersect calls,
+    Scene::occluded calls).  peel_first: only level 0 is looped; its children
+    are traced by oracle_trace_rays on a copy of the scene with recursion_limit
+    - 1 (Tracer::trace_recursive(child, 1)).  TEST ONLY."""
+    scatter = scatter or (lambda sc, r, h, m, depth: scatter_rays(sc, r, h, m, depth))
+    combine = combine or combine_bounce
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+    n = len(rays)
+    limit = int(scene.desc.recursion_limit)
+    if limit <= 0 or n == 0:
+        return np.zeros((n, 3)), [], 0, 0
+    levels, n_isect, n_occl, depth = [], 0, 0, 0
+    while True:
+        ok, hits = oracle_scene_intersect(scene, rays)
+        n_isect += len(rays)
+        rgb, no = oracle_shade_hits(scene, hits, rays_wo(rays), ok.astype(np.uint8))
+        n_occl += int(no.sum())
+        spawn, first, child, w = scatter(scene, rays, hits, ok.astype(np.uint8), depth)
+        levels.append([len(rays), rgb, spawn, first, w])
+        if len(child) == 0:
+            break
+        if peel_first:
+            sub = with_recursion_limit(scene, limit - 1)
+            crgb, ni, no = oracle_trace_rays(sub, child["o"], child["d"])
+            n_isect += int(ni.sum())
+            n_occl += int(no.sum())
+            levels.append([len(child), crgb, None, None, None])
+            break
+        rays, depth = child, depth + 1
+    for k in range(len(levels) - 2, -1, -1):
+        ln, rgb, spawn, first, w = levels[k]
+        levels[k][1] = combine(rgb, spawn, first, levels[k + 1][1], w)
+    return levels[0][1], [lv[0] for lv in levels], n_isect, n_occl
 
 
 def oracle_primary_hits(scene: Scene, W: int | None = None, H: int | None = None) -> np.ndarray:
