@@ -274,10 +274,26 @@ enum rt_flags {
                                    eager programs: wave-level culling without the wave
                                    BVH (A/B; results are identical).  No effect on
                                    smaller scenes, which never build the BVH.        */
-    RT_FLAG_FORCE_BVH = 16      /* a scene that has a wave BVH uses it on every frame.
+    RT_FLAG_FORCE_BVH = 16,     /* a scene that has a wave BVH uses it on every frame.
                                    Without this flag (or RT_FLAG_NO_BVH) the first two
                                    frames of a frame shape try it on and off and later
                                    frames take the faster (identical results). */
+    RT_FLAG_RAY_BVH = 32        /* rt_query_intersect / rt_query_occluded and their
+                                   _device forms: every ray walks a bounding-ball tree
+                                   over the scene's objects on its own instead of the
+                                   flat object list - for incoherent batches (baking,
+                                   probes, visibility) on scenes of many objects.  The
+                                   results are the bytes of the same call without the
+                                   flag (hits, masks, stats counts), non-finite rays
+                                   included.  It changes the kernel only for a scene
+                                   that has a wave list (more than 256 top-level
+                                   objects, no eager programs), without
+                                   RT_FLAG_NO_CULL, within the standard device stacks;
+                                   otherwise it is accepted and the flat kernel runs.
+                                   The tree is uploaded by the first such query of a
+                                   scene and stays resident with it.  The node,
+                                   radiance, shade and scatter calls and the frames
+                                   accept the bit and ignore it. */
 };
 
 /* Tracer::render: render the whole frame into a caller-owned host buffer of
@@ -448,7 +464,8 @@ typedef struct rt_hit {        /* 64 B; geometry.h:25-46 Hit */
  * the device and back in chunks of bounded size.  flags: RT_FLAG_NONE or
  * RT_FLAG_NO_CULL (identical results; RT_FLAG_NO_BVH / RT_FLAG_FORCE_BVH
  * have no effect: queries walk the flat object list, whose results equal the
- * wave BVH's); RT_FLAG_FP32 and RT_FLAG_COUNT_OPS are RT_ERR_UNSUPPORTED, as
+ * wave BVH's) or RT_FLAG_RAY_BVH (identical results: each ray walks the ray
+ * BVH, see rt_flags); RT_FLAG_FP32 and RT_FLAG_COUNT_OPS are RT_ERR_UNSUPPORTED, as
  * is a scene beyond the device stacks.  n == 0 is RT_OK without a launch.
  * stats (may be NULL): rays_intersect = rays_traced = n, ms_kernel, ms_total.
  * Uses the current HIP device and shares its resident scene copy with the

@@ -74,6 +74,29 @@ int rt_test_compile_forms(const struct rt_scene* s, int32_t* out, int cap);
 int rt_test_wave_bvh(const struct rt_scene* s, int32_t* counts, int32_t* worig, float* wctab, int cap_objs,
                      float* wchunk, int cap_chunks);
 
+/* Host-only: the ray BVH of a scene (RT_FLAG_RAY_BVH; CompiledScene::rnodes).
+ * counts[3] = {nodes, unbounded lead objects of the wave list (outside the
+ * tree: every ray evaluates them), objects in the wave list}; nodes 0: no tree.
+ * Up to cap nodes go to nodes_out, 32 bytes each: the f32 ball (cx, cy, cz, r),
+ * then int32 skip (the next node in depth-first pre-order when the subtree is
+ * culled; the node count at the end), first, count (a leaf's range of the
+ * wave list; an inner node has count 0) and a pad word. */
+int rt_test_ray_bvh(const struct rt_scene* s, int32_t* counts, void* nodes_out, int cap);
+/* Host-only: the kernels' walk restated on the host.  For each ray's fixed
+ * segment [tmin, tmax], cand_out[i * n_objects + k] = 1 for every top-level
+ * object k (an index into rt_scene_desc.objects) whose evaluation the walk
+ * reaches, else 0, and tests_out[i] = the ray's number of node tests (either
+ * may be NULL).  RT_ERR_UNSUPPORTED: the scene has no tree. */
+int rt_test_ray_bvh_walk(const struct rt_scene* s, const struct rt_ray* rays, size_t n, uint8_t* cand_out,
+                         int32_t* tests_out);
+/* The kernel ("ns::name") a ray query of kind 0 (intersect) / 1 (occluded) with
+ * these flags launches when RT_FLAG_RAY_BVH may be among them: the ray-BVH
+ * row where the flag takes effect (frame_plan.hpp use_ray_bvh), else the flat
+ * row rt_test_query_kernel_name reports; and row `index` of the ray-BVH table
+ * (rtd only).  Host only. */
+int rt_test_ray_bvh_kernel_name(const struct rt_scene* s, int kind, int flags, char* out, int cap);
+int rt_test_ray_bvh_row(int index, char* out, int cap);
+
 /* Resources of the trace kernel rt_render would launch for this scene, mode
  * and flags (hipFuncGetAttributes + occupancy query): out[8] = {VGPRs per
  * lane, scratch bytes per lane, LDS bytes per workgroup (static + the

@@ -2643,6 +2643,15 @@ __device__ __forceinline__ bool cone_touch(const float* g, const Cone& K) {
 #ifndef RT_CAM_RHO0
 #define RT_CAM_RHO0 1
 #endif
+// The merge of objects that arrive out of the reference's order (BV, and the
+// ray BVH's walk, rt_query_bvh_kernels.hpp): does the object at index oo of
+// the reference's order, hit at t (ok: within the range up to and including
+// closest), replace the winner so far (win < 0: none; win_orig its index,
+// win_tie whether it accepts t == tmax)?  tie: whether this object does.
+__device__ __forceinline__ bool closest_takes(bool ok, real t, real closest, int win, int oo, int win_orig, bool tie,
+                                              bool win_tie) {
+    return ok && ((t < closest) || (t == closest && (win < 0 ? tie : (oo > win_orig ? tie : !win_tie))));
+}
 template <bool EAGER, bool DEEP, bool BV = false, bool LEAD = false, bool CAM = false, bool KA = false, class CT>
 __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin, real tmax, real& t_best,
                                      DHit& best, bool wave_ok, CT& cnt, bool valid = true) {
@@ -2788,8 +2797,7 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
                                                         use_mask);
                 const int oo = S.worig[o];
                 const bool tie = rtamd::accepts_tie(ob);
-                const bool take = ok && ((t < closest) ||
-                                         (t == closest && (win < 0 ? tie : (oo > win_orig ? tie : !win_tie))));
+                const bool take = closest_takes(ok, t, closest, win, oo, win_orig, tie, win_tie);
                 if (take) {
                     closest = t;
                     win = o;

@@ -136,6 +136,22 @@ struct QueryParams {
 };
 enum { kQueryIsect = 0, kQueryOccl = 1, kQueryRadiance = 2 };   // query kinds (k_query_isect / k_query_occl / k_radiance)
 
+// The same batch on the per-ray BVH (RT_FLAG_RAY_BVH, rt_query_bvh_kernels.hpp):
+// the tree's nodes[0, n_nodes) over wobjs[n_lead, n_wobjs) (CompiledScene::rnodes
+// / rlead), resident next to the scene.  The launcher fills in the flat object
+// list (SceneView::objs / ctab / n_objs), which the kernels' fallback walks.
+struct RayBvhParams {
+    const rt_ray* rays;
+    size_t n;
+    rt_hit* hits;
+    uint8_t* mask;
+    const RayBvhNode* nodes;
+    int n_nodes, n_lead;
+    const DevObj* flat_objs;
+    const float* flat_ctab;
+    int n_flat;
+};
+
 // A batch of radiance queries (rt_query_radiance): ray i of rays[0, n) is lane
 // i % 64 of wave i / 64, rgb[3i .. 3i + 2] its colour (Tracer::trace); tmin /
 // tmax of the rays are not read.  counters: the frames' kCounterSlots x
@@ -268,6 +284,10 @@ RT_DECLARE_TABLES(rtd)
 RT_DECLARE_TABLES(rtf)    // (defines the frame tables only)
 RT_DECLARE_TABLES(rtdb)
 #undef RT_DECLARE_TABLES
+// The ray-BVH query kernels (rt_query_bvh_kernels.hpp): rtd only.  kind: kQueryIsect / kQueryOccl
+namespace rtd {
+const rtamd::KernelTable<rtamd::RayBvhParams>& ray_bvh_table();
+}
 
 namespace rtamd {
 // KernelVariant::ns -> its namespace: the one place that choice is written.
@@ -312,6 +332,11 @@ inline hipError_t launch_paper_finish(const KernelVariant& v, dim3 grid, hipStre
 inline hipError_t launch_query(const KernelVariant& v, int kind, hipStream_t st, const SceneView& V,
                                const QueryParams& P) {
     return launch_in(kernel_namespace(v.ns).query, v, kind, dim3(), st, V, P);
+}
+// (a variant outside rtd has no row there: hipErrorInvalidDeviceFunction)
+inline hipError_t launch_ray_bvh(const KernelVariant& v, int kind, hipStream_t st, const SceneView& V,
+                                 const RayBvhParams& P) {
+    return launch_in(&rtd::ray_bvh_table(), v, kind, dim3(), st, V, P);
 }
 inline hipError_t launch_radiance(const KernelVariant& v, hipStream_t st, const SceneView& V, const RadianceParams& P) {
     return launch_in(kernel_namespace(v.ns).radiance, v, 0, dim3(), st, V, P);

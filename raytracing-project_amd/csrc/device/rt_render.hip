@@ -214,6 +214,11 @@ struct Workspace {
     // node queries: the programs of the resident scene's nodes queried so far, by
     // (node, kind); emptied with the resident scene (release_node_programs)
     std::map<std::pair<int, int>, NodeProg> node_progs;
+    // ray queries with RT_FLAG_RAY_BVH: the resident scene's ray BVH
+    // (CompiledScene::rnodes), uploaded by the first such query of the scene
+    // and emptied with it (release_ray_bvh)
+    DBuf rnodes;
+    bool rnodes_resident = false;
     DBuf q_lights;                            // a shading query's own point lights (never the resident scene's `lights`)
     DBuf cam_rows;                            // rt_camera_rays, centre rays: a rows list that is not 0, 1, 2, ...
     DBuf scatter_tmp;                         // rt_scatter_rays_device: a launch group's child total + its scan's words
@@ -366,6 +371,32 @@ void release_node_programs(Workspace& ws) {
     ws.node_progs.clear();
 }
 
+// The ray BVH belongs to the resident scene as the node programs do.
+void release_ray_bvh(Workspace& ws) {
+    ws.rnodes.release();
+    ws.rnodes_resident = false;
+}
+
+// The resident scene's ray BVH, resident too: uploaded on st by the first
+// flagged ray query of the scene, which counts in rt_setup_times[0] like the
+// scene's own upload; later ones find it.  Frames and unflagged queries never
+// come here.  The caller holds the workspace lock, has reset the staging arena
+// and made the scene resident.
+int ray_bvh_resident(Workspace& ws, hipStream_t st) {
+    if (ws.rnodes_resident) return RT_OK;
+    const auto t_up = SClock::now();
+    struct AddTime {
+        SClock::time_point t;
+        ~AddTime() {
+            std::lock_guard<std::mutex> lk(g_setup.mu);
+            g_setup.scene_ms += ms_since(t);
+        }
+    } add_time{t_up};
+    HIP_TRY(upload(ws.rnodes, ws.sc.cs.rnodes, st, &ws.up));
+    ws.rnodes_resident = true;
+    return RT_OK;
+}
+
 // The scene resident in the workspace: compiled and uploaded once (on st), and
 // found there by every later frame or ray query of it on the device.  The
 // caller holds the workspace lock and has reset the staging arena.
@@ -384,6 +415,7 @@ int scene_resident(Workspace& ws, const rt_scene* s, const rt_scene_desc& d, boo
     } add_scene_time{t_sc};
     sc.valid = false;
     release_node_programs(ws);
+    release_ray_bvh(ws);
     try {
         sc.cs = rtamd::compile_scene(d);
     } catch (const std::exception& e) {
@@ -930,7 +962,8 @@ int render_rows_impl(const rt_scene* s, int W, int H, int mode, int flags, const
 constexpr size_t kLaunchItems = (size_t)1 << 30;
 constexpr size_t kChunkItems = (size_t)1 << 20;
 std::atomic<size_t> g_chunk_items{kChunkItems};
-constexpr int kKnownFlags = RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH;
+constexpr int kKnownFlags =
+    RT_FLAG_COUNT_OPS | RT_FLAG_NO_CULL | RT_FLAG_FP32 | RT_FLAG_NO_BVH | RT_FLAG_FORCE_BVH | RT_FLAG_RAY_BVH;
 
 // One batched call on stream st.  Made first (it takes the call's start time);
 // zero_stats() once the arguments that are checked before the stats are fine;
@@ -1085,6 +1118,12 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
     if (rv != RT_OK) return rv;
     if (depth) S.rec_limit = at_depth.recursion_limit;
     Workspace& ws = *call.ws;
+    // RT_FLAG_RAY_BVH: the ray-BVH row of the variant where the scene has the tree (frame_plan.hpp use_ray_bvh)
+    const bool ray_bvh = !radiance && rtamd::use_ray_bvh(ws.sc.cs, kv, flags);
+    if (ray_bvh) {
+        rv = ray_bvh_resident(ws, st);
+        if (rv != RT_OK) return rv;
+    }
     const size_t chunk = host ? std::min(n, g_chunk_items.load()) : n;
     if (host) {
         HIP_TRY(ws.q_rays.ensure(chunk * sizeof(rt_ray)));
@@ -1111,6 +1150,16 @@ int query_impl(const char* what, const rt_scene* s, int kind, const rt_ray* rays
                 P.rgb = d_rgb + 3 * l0;
                 P.counters = ws.counters.as<unsigned long long>();
                 HIP_TRY(rtamd::launch_radiance(kv, st, S, P));
+            } else if (ray_bvh) {
+                rtamd::RayBvhParams P{};
+                P.n = ln;
+                P.rays = d_rays + l0;
+                P.hits = d_hits ? d_hits + l0 : nullptr;
+                P.mask = d_mask ? d_mask + l0 : nullptr;
+                P.nodes = ws.rnodes.as<rtamd::RayBvhNode>();
+                P.n_nodes = (int)ws.sc.cs.rnodes.size();
+                P.n_lead = ws.sc.cs.rlead;
+                HIP_TRY(rtamd::launch_ray_bvh(kv, kind, st, S, P));
             } else {
                 QueryParams P;
                 P.n = ln;
@@ -1627,6 +1676,7 @@ int rtamd::release_device_workspaces(int min_slot) {
                         &w->scatter_tmp})
             b->release();
         release_node_programs(*w);
+        release_ray_bvh(*w);
         w->jtab.release();
         w->jcache.release();   // every cached entry and the uncached buffer (the hit / miss counts stay)
         w->counters_zero = false;

@@ -249,6 +249,71 @@ extern "C" int rt_test_query_kernel_name(const rt_scene* s, int kind, int flags,
                        [=](const KernelVariant& v) { return kernel_in(rtamd::kernel_namespace(v.ns).query, v, kind); });
 }
 
+// ------------------------------------------------------------------ ray BVH
+extern "C" int rt_test_ray_bvh_kernel_name(const rt_scene* s, int kind, int flags, char* out, int cap) {
+    if (!s || !out || cap <= 0 || (kind != rtamd::kQueryIsect && kind != rtamd::kQueryOccl)) return RT_ERR_INVALID_ARG;
+    try {
+        const rt_scene_desc& d = *rt_scene_get_desc(s);
+        const rtamd::CompiledScene cs = rtamd::compile_scene(d);
+        KernelVariant v;
+        const int rc = rtamd::pick_query_variant(cs, d, flags, &v);
+        if (rc != RT_OK) return rc;
+        const rtamd::KernelEntry k = rtamd::use_ray_bvh(cs, v, flags)
+                                         ? kernel_in(&rtd::ray_bvh_table(), v, kind)
+                                         : kernel_in(rtamd::kernel_namespace(v.ns).query, v, kind);
+        if (!k.name) {
+            rtamd::set_last_error("rt_test_ray_bvh_kernel_name: no kernel for this variant");
+            return RT_ERR_UNSUPPORTED;
+        }
+        std::snprintf(out, (size_t)cap, "%s::%s", rtamd::variant_ns_name(v.ns), k.name);
+        return RT_OK;
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("scene compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+}
+
+extern "C" int rt_test_ray_bvh_row(int index, char* out, int cap) {
+    const char* name = out && cap > 0 && index >= 0 ? rtd::ray_bvh_table().row_name(index) : nullptr;
+    if (!name) return RT_ERR_INVALID_ARG;
+    std::snprintf(out, (size_t)cap, "rtd::%s", name);
+    return RT_OK;
+}
+
+extern "C" int rt_test_ray_bvh(const rt_scene* s, int32_t* counts, void* nodes_out, int cap) {
+    if (!s || !counts || cap < 0 || (cap > 0 && !nodes_out)) return RT_ERR_INVALID_ARG;
+    try {
+        const rtamd::CompiledScene cs = rtamd::compile_scene(*rt_scene_get_desc(s));
+        const int n = (int)cs.rnodes.size();
+        counts[0] = n;
+        counts[1] = cs.rlead;
+        counts[2] = (int32_t)cs.wobjs.size();
+        if (n && cap) std::memcpy(nodes_out, cs.rnodes.data(), (size_t)std::min(n, cap) * sizeof(rtamd::RayBvhNode));
+        return RT_OK;
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("scene compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+}
+
+extern "C" int rt_test_ray_bvh_walk(const rt_scene* s, const rt_ray* rays, size_t n, uint8_t* cand_out,
+                                    int32_t* tests_out) {
+    if (!s || (n && !rays)) return RT_ERR_INVALID_ARG;
+    try {
+        const rt_scene_desc& d = *rt_scene_get_desc(s);
+        const rtamd::CompiledScene cs = rtamd::compile_scene(d);
+        if (cand_out) std::memset(cand_out, 0, n * (size_t)d.n_objects);
+        if (!rtamd::ray_bvh_walk(cs, rays, n, d.n_objects, cand_out, tests_out)) {
+            rtamd::set_last_error("rt_test_ray_bvh_walk: the scene has no ray BVH");
+            return RT_ERR_UNSUPPORTED;
+        }
+        return RT_OK;
+    } catch (const std::exception& e) {
+        rtamd::set_last_error(std::string("scene compile: ") + e.what());
+        return RT_ERR_INVALID_ARG;
+    }
+}
+
 extern "C" int rt_test_radiance_kernel_name(const rt_scene* s, int flags, char* out, int cap) {
     return kernel_name("rt_test_radiance_kernel_name", s, out, cap, query_pick(rtamd::pick_radiance_variant, flags),
                        [](const KernelVariant& v) { return kernel_in(rtamd::kernel_namespace(v.ns).radiance, v); });

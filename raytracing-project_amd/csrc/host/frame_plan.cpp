@@ -140,6 +140,11 @@ int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flag
     return RT_OK;
 }
 
+bool use_ray_bvh(const CompiledScene& cs, const KernelVariant& v, int flags) {
+    return (flags & RT_FLAG_RAY_BVH) && !(flags & RT_FLAG_NO_CULL) && !cs.rnodes.empty() && !v.eager &&
+           v.ns == KernelVariant::kRtd;
+}
+
 int pick_shade_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out) {
     // (shade()'s only scene walk is Scene::occluded: the occluded query's rule)
     return pick_query_variant(cs, d, flags, out);

@@ -70,6 +70,12 @@ int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int 
 // before anything else), or a scene beyond the big stacks.
 int check_query_flags(int flags);
 int pick_query_variant(const CompiledScene& cs, const rt_scene_desc& d, int flags, KernelVariant* out);
+// Whether a ray query of variant v (pick_query_variant's) launches the ray-BVH
+// row of (D, PL) (rt_query_bvh_kernels.hpp) instead of the flat one:
+// RT_FLAG_RAY_BVH without RT_FLAG_NO_CULL, a scene with a ray BVH (it has a
+// wave list: more than kWaveBvhMin objects, no eager programs) and the
+// namespace rtd.  In every other case the flag is accepted and changes nothing.
+bool use_ray_bvh(const CompiledScene& cs, const KernelVariant& v, int flags);
 
 // The variant a shading query (rt_query_shade: shade_lambert_phong of
 // caller-given hits) of (scene, flags) launches: pick_query_variant's rule, as

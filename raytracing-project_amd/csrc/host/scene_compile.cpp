@@ -562,6 +562,7 @@ public:
             cs.n_lead = ok ? (int)lead : 0;
         }
         build_wave_bvh(cs);
+        build_ray_bvh(cs);
         light_records(cs.ctab.data(), cs.objs.size(), 8, d_.lights, d_.n_lights, cs.lrec);
         light_records(cs.wctab.data(), cs.wobjs.size(), 8, d_.lights, d_.n_lights, cs.lwrec);
         light_records(cs.gbounds.data(), cs.gbounds.size() / 4, 4, d_.lights, d_.n_lights, cs.lgb);
@@ -662,6 +663,109 @@ public:
             }
             std::memcpy(&rec[4], &type, sizeof(int));
         }
+    }
+
+    // The ray BVH (CompiledScene::rnodes; ray_bvh_rules.hpp): a binary tree
+    // over the bounded part of the wave list, split at the middle of each
+    // range of its Morton order (rounded to whole leaves of kRayBvhLeaf
+    // objects), emitted in depth-first pre-order with each node's skip index.
+    // A node's ball is centred on the box of its objects' f32 balls and holds
+    // every one of them: the radius is rounded outward until
+    // |c_node - c_obj| + r_obj <= r_node holds in double from the stored
+    // floats.  A range whose balls are not finite gets the ball (0, inf),
+    // which every ray touches.
+    static void ray_bvh_ball(const CompiledScene& cs, int a, int b, float out[4]) {
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int i = a; i < b; ++i) {
+            const float* f = cs.wobjs[i].fb;
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = std::min(lo[k], (double)f[k] - (double)f[3]);
+                hi[k] = std::max(hi[k], (double)f[k] + (double)f[3]);
+            }
+        }
+        for (int k = 0; k < 3; ++k) out[k] = (float)(0.5 * (lo[k] + hi[k]));
+        auto reach = [&](int i) {   // of object i's ball from the stored centre
+            const float* f = cs.wobjs[i].fb;
+            const double dx = (double)out[0] - (double)f[0], dy = (double)out[1] - (double)f[1],
+                         dz = (double)out[2] - (double)f[2];
+            return std::sqrt(dx * dx + dy * dy + dz * dz) + (double)f[3];
+        };
+        double R = 0.0;
+        for (int i = a; i < b; ++i) R = std::max(R, reach(i));
+        if (!std::isfinite(R) || !std::isfinite(out[0]) || !std::isfinite(out[1]) || !std::isfinite(out[2])) {
+            out[0] = out[1] = out[2] = 0.0f;
+            out[3] = INFINITY;
+            return;
+        }
+        float r = std::nextafter((float)(R * (1.0 + 1e-7)), INFINITY);
+        for (int i = a; i < b; ++i)
+            while (!(reach(i) <= (double)r)) r = std::nextafter(r, INFINITY);
+        out[3] = r;
+    }
+    // Where [a, b) of the Morton order splits: the position, within the middle
+    // three quarters of the range (so that the depth stays logarithmic), with
+    // the least surface-area cost area(left box) * n_left + area(right box) *
+    // n_right over the boxes of the objects' f32 balls.  Morton order keeps
+    // neighbours together but jumps between cells; a split at such a jump
+    // gives two compact children where the middle of the range may not.  The
+    // middle when no cost is finite.
+    static int ray_bvh_split(const CompiledScene& cs, int a, int b) {
+        const int n = b - a, margin = std::max(1, n / 8);
+        struct Box {
+            double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+            void add(const float* f) {
+                for (int k = 0; k < 3; ++k) {
+                    lo[k] = std::min(lo[k], (double)f[k] - (double)f[3]);
+                    hi[k] = std::max(hi[k], (double)f[k] + (double)f[3]);
+                }
+            }
+            double area() const {
+                const double x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
+                return x * y + y * z + z * x;
+            }
+        };
+        std::vector<double> right((size_t)n + 1, 0.0);   // right[i]: area of the box of [a + i, b)
+        Box r;
+        for (int i = n - 1; i >= 1; --i) {
+            r.add(cs.wobjs[a + i].fb);
+            right[i] = r.area();
+        }
+        int best = a + (n + 1) / 2;
+        double best_cost = INFINITY;
+        Box l;
+        for (int i = 1; i < n; ++i) {
+            l.add(cs.wobjs[a + i - 1].fb);
+            if (i < margin || n - i < margin) continue;
+            const double cost = l.area() * i + right[i] * (n - i);
+            if (cost < best_cost) {
+                best_cost = cost;
+                best = a + i;
+            }
+        }
+        return best;
+    }
+    static void ray_bvh_emit(CompiledScene& cs, int a, int b) {
+        const size_t idx = cs.rnodes.size();
+        cs.rnodes.push_back(RayBvhNode{});
+        RayBvhNode nd{};
+        ray_bvh_ball(cs, a, b, nd.c);
+        if (b - a <= kRayBvhLeaf) {
+            nd.first = a;
+            nd.count = b - a;
+        } else {
+            const int s = ray_bvh_split(cs, a, b);
+            ray_bvh_emit(cs, a, s);
+            ray_bvh_emit(cs, s, b);
+        }
+        nd.skip = (int32_t)cs.rnodes.size();
+        cs.rnodes[idx] = nd;
+    }
+    static void build_ray_bvh(CompiledScene& cs) {
+        const int n = (int)cs.wobjs.size();
+        int lead = 0;
+        while (lead < n && !cs.wobjs[lead].has_bound) ++lead;
+        cs.rlead = lead;
+        if (lead < n) ray_bvh_emit(cs, lead, n);
     }
 
     // Wave-uniform cull groups over runs of consecutive bounded objects.  A run
@@ -766,6 +870,53 @@ CompiledScene compile_scene(const rt_scene_desc& d) {
 NodeProgram compile_node_program(const rt_scene_desc& d, int node, int kind) {
     Compiler c(d);
     return c.node_program(node, kind);
+}
+
+bool ray_bvh_walk(const CompiledScene& cs, const rt_ray* rays, size_t n, int n_objects, uint8_t* cand, int32_t* tests) {
+    if (cs.rnodes.empty()) return false;
+    // objs holds the top-level objects in order, group headers between them
+    std::vector<int> top(cs.objs.size(), -1);
+    int k = 0;
+    for (size_t j = 0; j < cs.objs.size(); ++j)
+        if (cs.objs[j].kind != OBJ_GROUP) top[j] = k++;
+    const int n_nodes = (int)cs.rnodes.size();
+    for (size_t i = 0; i < n; ++i) {
+        const rt_ray& R = rays[i];
+        // Ray(o, d) (core.h:278): the direction normalised, as the kernels' make_ray
+        double d[3] = {R.d[0], R.d[1], R.d[2]};
+        const double L = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        if (L > 1e-6) {
+            for (double& c : d) c = c / L;
+        } else {
+            d[0] = 0.0, d[1] = 1.0, d[2] = 0.0;
+        }
+        const float ox = (float)R.o[0], oy = (float)R.o[1], oz = (float)R.o[2];
+        const float dx = (float)d[0], dy = (float)d[1], dz = (float)d[2];
+        const float t0 = (float)R.tmin, t1 = (float)R.tmax;
+        uint8_t* row = cand ? cand + i * (size_t)n_objects : nullptr;
+        auto reach = [&](int w) {
+            const int t = cs.worig[w] >= 0 ? top[cs.worig[w]] : -1;
+            if (row && t >= 0 && t < n_objects) row[t] = 1;
+        };
+        for (int w = 0; w < cs.rlead; ++w)
+            if (cs.wobjs[w].kind != OBJ_NEVER) reach(w);
+        int32_t nt = 0;
+        for (int j = 0; j < n_nodes;) {
+            const RayBvhNode& nd = cs.rnodes[j];
+            ++nt;
+            if (!ray_bvh_touch(nd.c[0], nd.c[1], nd.c[2], nd.c[3], ox, oy, oz, dx, dy, dz, t0, t1)) {
+                j = nd.skip;
+                continue;
+            }
+            for (int w = nd.first; w < nd.first + nd.count; ++w) {
+                const float* f = cs.wobjs[w].fb;
+                if (ray_bvh_touch(f[0], f[1], f[2], f[3], ox, oy, oz, dx, dy, dz, t0, t1)) reach(w);
+            }
+            ++j;
+        }
+        if (tests) tests[i] = nt;
+    }
+    return true;
 }
 
 }  // namespace rtamd

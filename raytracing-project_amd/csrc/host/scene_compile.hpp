@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "ray_bvh_rules.hpp"
 #include "rt.h"
 
 namespace rtamd {
@@ -107,6 +108,14 @@ struct CompiledScene {
     std::vector<float> wctab;
     std::vector<int32_t> worig;
     std::vector<float> wchunk;
+    // Ray BVH (RT_FLAG_RAY_BVH; DESIGN.md §Ray BVH; ray_bvh_rules.hpp): a binary
+    // tree of balls over wobjs[rlead, n), the bounded part of the wave list in
+    // its Morton order, in depth-first pre-order, walked by each ray on its own
+    // (rt_query_bvh_kernels.hpp).  wobjs[0, rlead) - the unbounded objects and
+    // their padding - are outside it: every ray evaluates them first.  Built
+    // with the wave list; empty without one.
+    std::vector<RayBvhNode> rnodes;
+    int rlead = 0;
     // Light-relative shadow cull records (light_records, scene_compile.cpp):
     // [light][record] x 8 floats for ctab (lrec), wctab (lwrec) and every
     // gbounds ball (lgb); the shadow-query culls of scene_occluded_wave.
@@ -141,6 +150,14 @@ inline bool accepts_tie(const DevObj& o) {
 
 // Throws std::runtime_error on malformed IR.
 CompiledScene compile_scene(const rt_scene_desc& d);
+
+// The ray BVH's walk on the host, the kernels' rule restated (no device): for
+// ray i's fixed segment [tmin, tmax], cand[i * n_objects + k] = 1 for every
+// top-level object k (an index into rt_scene_desc::objects) whose evaluation
+// the walk reaches - the lead objects, and the objects of touched leaves whose
+// own f32 ball the segment touches - and tests[i] = its number of node tests.
+// Either output may be null.  false: the scene has no ray BVH.
+bool ray_bvh_walk(const CompiledScene& cs, const rt_ray* rays, size_t n, int n_objects, uint8_t* cand, int32_t* tests);
 
 // One node's own program (rt_query_node_intersect / rt_query_node_interval):
 // the post-order eager program with full hit records of the subtree under

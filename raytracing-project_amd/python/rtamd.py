@@ -47,6 +47,7 @@ RT_FLAG_NO_CULL = 2
 RT_FLAG_FP32 = 4   # non-parity FP32 fast path
 RT_FLAG_NO_BVH = 8   # wave culls without the wave BVH (A/B; identical results)
 RT_FLAG_FORCE_BVH = 16   # the wave BVH on every frame (no on/off trial frames)
+RT_FLAG_RAY_BVH = 32   # ray queries: every ray walks the ray BVH on its own (identical results)
 RT_RAYS_CENTRE = 0     # rt_camera_rays: Camera::generate_ray at the pixel centres
 RT_RAYS_JITTERED = 1   # ... generate_ray_subpixel at the frame's own RT_SPP jitter draws per pixel
 RT_SPP = 8             # samples per pixel of a standard frame (tracer.cpp:283)
@@ -914,14 +915,83 @@ def query_intersect_device(scene: Scene, rays_dev: DeviceBuffer, n: int, hits_de
         raise RTError(rc, last_error())
 
 
+def query_occluded_device(scene: Scene, rays_dev: DeviceBuffer, n: int, occluded_dev: DeviceBuffer,
+                          flags: int = RT_FLAG_NONE, stream: Stream | None = None, stats: Stats | None = None) -> None:
+    """rt_query_occluded_device: the first n rt_ray records of rays_dev into n
+    flag bytes of occluded_dev, on `stream` (None: the default stream)."""
+    if n < 0 or rays_dev.nbytes < n * RAY_DTYPE.itemsize or occluded_dev.nbytes < n:
+        raise ValueError("query_occluded_device: a buffer is too small for n rays")
+    st = stats if stats is not None else Stats()
+    rc = amd_lib().rt_query_occluded_device(scene.handle, rays_dev.ptr, n, flags, occluded_dev.ptr,
+                                            stream.handle if stream else None, C.byref(st))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+
+
 def query_kernel_name(scene: Scene, kind: int, flags: int = RT_FLAG_NONE) -> tuple[int, str]:
     """rt_test_query_kernel_name: (status, "ns::kernel") of the kernel a query
     of kind 0 (intersect) / 1 (occluded) launches.  Host only."""
     return _kernel_name("rt_test_query_kernel_name", scene, kind, flags)
 
 
+# ------------------------------------------------------------------ ray BVH
+RAY_BVH_NODE_DTYPE = np.dtype([("c", "<f4", (4,)), ("skip", "<i4"), ("first", "<i4"), ("count", "<i4"),
+                               ("pad", "<i4")])   # RayBvhNode (ray_bvh_rules.hpp)
+assert RAY_BVH_NODE_DTYPE.itemsize == 32
+
+
+def ray_bvh_kernel_name(scene: Scene, kind: int, flags: int = RT_FLAG_RAY_BVH) -> tuple[int, str]:
+    """rt_test_ray_bvh_kernel_name: (status, "ns::kernel") of the kernel a ray
+    query of kind 0 (intersect) / 1 (occluded) launches with these flags: the
+    ray-BVH row where RT_FLAG_RAY_BVH takes effect, else the flat row.  Host only."""
+    return _kernel_name("rt_test_ray_bvh_kernel_name", scene, kind, flags)
+
+
+def ray_bvh_rows() -> list[str]:
+    """rt_test_ray_bvh_row: the rows ("rtd::kernel") of the ray-BVH launch table.  Host only."""
+    fn = amd_lib().rt_test_ray_bvh_row
+    fn.argtypes = [C.c_int, C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(160)
+    out = []
+    while fn(len(out), buf, 160) == RT_OK:
+        out.append(buf.value.decode())
+    return out
+
+
+def ray_bvh_nodes(scene: Scene) -> tuple[np.ndarray, int, int]:
+    """rt_test_ray_bvh: (nodes (RAY_BVH_NODE_DTYPE), lead, n_wave) of the scene's
+    ray BVH: the tree lies over objects [lead, n_wave) of the wave list.  No
+    tree: an empty node array.  Host only."""
+    lib = amd_lib()
+    lib.rt_test_ray_bvh.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int]
+    counts = (C.c_int32 * 3)()
+    _ok(lib.rt_test_ray_bvh(scene.handle, counts, None, 0), "rt_test_ray_bvh")
+    nodes = np.zeros(int(counts[0]), dtype=RAY_BVH_NODE_DTYPE)
+    if len(nodes):
+        _ok(lib.rt_test_ray_bvh(scene.handle, counts, nodes.ctypes.data_as(C.c_void_p), len(nodes)), "rt_test_ray_bvh")
+    return nodes, int(counts[1]), int(counts[2])
+
+
+def ray_bvh_walk(scene: Scene, origins, dirs, tmin=1e-4, tmax=np.inf) -> tuple[np.ndarray, np.ndarray]:
+    """rt_test_ray_bvh_walk: (reached (n, n_objects) bool, node tests (n,)) of
+    the kernels' walk restated on the host, for each ray's fixed segment
+    [tmin, tmax]: the top-level objects whose evaluation the walk reaches.
+    Raises RTError (RT_ERR_UNSUPPORTED) for a scene without a tree.  Host only."""
+    lib = amd_lib()
+    lib.rt_test_ray_bvh_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    rays = make_rays(origins, dirs, tmin, tmax)
+    n, n_obj = len(rays), int(scene.desc.n_objects)
+    cand = np.zeros((n, n_obj), dtype=np.uint8)
+    tests = np.zeros(n, dtype=np.int32)
+    rc = lib.rt_test_ray_bvh_walk(scene.handle, rays.ctypes.data_as(C.c_void_p), n, cand.ctypes.data_as(C.c_void_p),
+                                  tests.ctypes.data_as(C.c_void_p))
+    if rc != RT_OK:
+        raise RTError(rc, last_error())
+    return cand.astype(bool), tests
+
+
 # ------------------------------------------------------------- node queries
-NODE_ISECT, NODE_IVL = 0, 1   # node query kinds (scene_compile.hpp kNodeIsect / kNodeIvl)
+NODE_ISECT, NODE_IVL = 0, 1  # node query kinds (scene_compile.hpp kNodeIsect / kNodeIvl)
 
 
 def query_node_intersect(scene: Scene, node: int, origins, dirs, tmin=1e-4, tmax=np.inf, flags: int = RT_FLAG_NONE,
