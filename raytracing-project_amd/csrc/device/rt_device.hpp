@@ -1823,9 +1823,13 @@ __device__ __forceinline__ bool cone_touch_t(const float4 g, float gmag, const C
     const float wa = LINE ? __builtin_fabsf(wa0) : wa0;
     // angle(w, a) <= theta + asin(R / |w|)  <=>  w.a >= cos(theta) sqrt(L2 - R^2) - sin(theta) R;
     // !(L2 > R^2): the bundle's origin region touches the ball (or NaN).  No
-    // branch: lanes disagree on the first test.
-    const float rhs = K.cth * sqrt_cull(L2 - R * R) - K.sth * R;
-    return !(L2 > R * R) | !(wa + m < rhs);
+    // branch: lanes disagree on the first test.  d = L2 - R^2 in one rounding
+    // (its sign is exact).  !(d < inf): a centre beyond 1.8e19 whose |w|^2
+    // overflows while R^2 does not leaves rhs infinite, and no finite w.a
+    // says anything against it: the ball passes.
+    const float d = __builtin_fmaf(-R, R, L2);
+    const float rhs = K.cth * sqrt_cull(d) - K.sth * R;
+    return !(d > 0.0f) | !(wa + m < rhs) | !(d < RT_INF_F);
 }
 __device__ __forceinline__ bool line_touch(const float* g, const Cone& K) {
     const float4 b = *reinterpret_cast<const float4*>(g);

@@ -826,6 +826,229 @@ def graph_scene(seed: int, dpi: int = 16) -> dict:
     return _base(objs, recursion=3, dpi=dpi, lights=lights)
 
 
+# ------------------------------------------------------------ forest scenes
+# Scalings of forest_scene: mirrors and anisotropic factors whose largest ratio
+# is 4, so that two nested ones stay within the ratio of 16 up to which a
+# Scaling keeps its bound (scene_compile.cpp xform_ball).
+_FOREST_FACTORS = ([-1, 1, 1], [1, -1, 1], [-1, -1, -1], [0.5, 2, 1], [1.3, 0.7, 1.0], [2, 0.5, -1.5], [0.8, 0.8, 1.25])
+_FOREST_ANGLES = (30, 90, 180, -45, 270)
+FOREST_SUN = ([-0.4, -1.0, -0.3], [0.9, 0.85, 0.8])    # the sun of dir_light_cases
+FOREST_SEEDS = (1, 2, 3, 4)
+_FOREST_LIGHTS = [{"position": [4, 6, 3], "intensity": [30, 30, 30]}, {"position": [-5, 5, 2], "intensity": [20, 20, 20]},
+                  {"position": [0, 8, -4], "intensity": [15, 15, 15]}]
+
+
+def forest_scene(seed: int, n: int, n_unbounded: int = 1, eager: bool = False, dpi: int = 16) -> dict:
+    """A seeded scene of n top-level objects of mixed compiled forms behind
+    n_unbounded half-space floors (y = -1.4 - 0.01 k), for the wave BVH and the
+    ray BVH (more than 256 objects; tests/test_forest_scenes.py,
+    tests/test_gpu_forest.py).  The objects stand on a jittered
+    ceil(sqrt(n))-square lattice that fills the view (x in [-3.4, 3.4], z from
+    -1.5 to -7.5, y in [-1.1, 1.4], radius in [0.08, 0.2]); each is a leaf
+    (about 35 %: a sphere, one in five a pokeball), an n-ary union, difference
+    or intersection of 2-4 leaves (25 %; the last two now and then with a
+    half-space as last operand), one transform over a leaf (20 %) or over such
+    a CSG (13 %), or two nested transforms over a leaf (7 %).  A transform's
+    subject is placed so that its image lands on the lattice point, as in
+    graph_scene.  No transform stands inside a CSG operand, so no object
+    compiles to an eager program; eager=True appends exactly one that does.
+    10 % of the materials are reflective, 8 % refractive; recursion 2, three
+    lights."""
+    import random
+    rnd = random.Random(seed)
+
+    def col():
+        m = _mat([rnd.random(), rnd.random(), rnd.random()], shininess=rnd.choice([4, 8, 16, 32]))
+        u = rnd.random()
+        if u < 0.10:
+            m["reflected"] = [0.5, 0.5, 0.5]
+        elif u < 0.18:
+            m["refracted"] = [0.6, 0.6, 0.6]
+        return m
+
+    def leaf(c, r):
+        if rnd.random() < 0.2:
+            return {"pokeball": {"position": list(c), "radius": r,
+                                 "button_dir": [rnd.uniform(-1, 1), rnd.uniform(-1, 1), 1.0]}}
+        return {"sphere": {"position": list(c), "radius": r, "color": col(), "index": rnd.choice([1.0, 1.33, 1.5])}}
+
+    def csg(c, r):
+        op = rnd.choice(["union", "difference", "intersection"])
+        spread = 0.8 if op == "union" else 0.45
+        kids = [leaf(c, r)]
+        kids += [leaf([c[i] + rnd.uniform(-spread, spread) * r for i in range(3)], rnd.uniform(0.5, 0.9) * r)
+                 for _ in range(rnd.randint(1, 3))]
+        if op != "union" and rnd.random() < 0.25:
+            kids.append(_half([c[i] + rnd.uniform(-0.3, 0.3) * r for i in range(3)],
+                              [rnd.uniform(-1, 1), 1.0, rnd.uniform(-1, 1)], col()))
+        return {op: kids}
+
+    def xform(c, r, levels, core):
+        if levels == 0:
+            return core(c, r)
+        k = rnd.randint(0, 2)
+        if k == 0:
+            f = [rnd.uniform(-1.5, 1.5) for _ in range(3)]
+            return _tr(f, xform([c[i] - f[i] for i in range(3)], r, levels - 1, core))
+        if k == 1:
+            ang, ax = rnd.choice(_FOREST_ANGLES), rnd.randint(0, 2)
+            a = -math.radians(ang)
+            i, j = [(1, 2), (2, 0), (0, 1)][ax]
+            q = list(c)
+            q[i] = math.cos(a) * c[i] - math.sin(a) * c[j]
+            q[j] = math.sin(a) * c[i] + math.cos(a) * c[j]
+            return _rot(ang, ax, xform(q, r, levels - 1, core))
+        f = rnd.choice(_FOREST_FACTORS)
+        g = abs(f[0] * f[1] * f[2]) ** (1.0 / 3.0)
+        return _sc(f, xform([c[i] / f[i] for i in range(3)], r / g, levels - 1, core))
+
+    objs = [_half([0, -1.4 - 0.01 * k, 0], [0, 1, 0], col()) for k in range(n_unbounded)]
+    side = max(1, math.ceil(math.sqrt(n)))
+    for k in range(n):
+        i, j = k % side, k // side
+        c = [-3.4 + 6.8 * (i + 0.5 + rnd.uniform(-0.3, 0.3)) / side, rnd.uniform(-1.1, 1.4),
+             -1.5 - 6.0 * (j + 0.5 + rnd.uniform(-0.3, 0.3)) / side]
+        r = rnd.uniform(0.08, 0.2)
+        u = rnd.random()
+        if u < 0.35:
+            objs.append(leaf(c, r))
+        elif u < 0.60:
+            objs.append(csg(c, r))
+        elif u < 0.80:
+            objs.append(xform(c, r, 1, leaf))
+        elif u < 0.93:
+            objs.append(xform(c, r, 1, csg))
+        else:
+            objs.append(xform(c, r, 2, leaf))
+    if eager:
+        c = [0.2, 0.4, -1.2]
+        objs.append({"union": [leaf(c, 0.2), _tr([0.3, 0.1, 0.0], leaf([c[0] - 0.1, c[1] - 0.1, c[2]], 0.15))]})
+    return _base(objs, recursion=2, dpi=dpi, lights=copy.deepcopy(_FOREST_LIGHTS))
+
+
+FOREST_TIE_KINDS = ("tr/rot", "rot/sc", "sc/tr", "rot/tr_union", "tr_union/tr")
+
+
+def forest_tie_scene(dpi: int = 16, reverse=()) -> dict:
+    """The lattice of bvh_scenes' ties with pairs of coincident objects of
+    other compiled forms, pair k of kind FOREST_TIE_KINDS[k % 5], every second
+    run of five in the other order.  The chain forms - the sphere under
+    Translation [0, 0, 0] (tr), Rotation 0 (rot), Scaling [1, 1, 1] (sc), and
+    Translation [0, 0, 0] over the far-sphere union of ties (tr_union) - give
+    the same first-hit t as each other, so those pairs tie exactly and the
+    reference's object order decides.  A chain against the bare sphere or the
+    bare union, which do not normalise the ray's direction anew, is left out:
+    their t differ in the last bits on about half the rays (5.417072566979102
+    against ...124 on one), which any rounding of the ray turns over - a shift
+    of the origin by 1e-7, or the second normalisation of rtamd.oracle_trace's
+    camera - and where the two do tie the sphere wins in either order, so the
+    pair says nothing about order.
+    reverse: the pair kinds whose pairs stand in the other order."""
+    objs = [_half([0, -1.4, 0], [0, 1, 0], _mat([0.5, 0.5, 0.5]))]
+    for k in range(150):
+        i, j = k % 15, k // 15
+        c = [-3.5 + 0.5 * i, -1.0 + 0.3 * j, -2.5 - 0.5 * j]
+        r = 0.18 + 0.04 * (k % 3)
+
+        def bare(col):
+            return {"sphere": {"position": list(c), "radius": r, "color": _mat(col)}}
+
+        def wrapped(col, side):
+            far = {"sphere": {"position": [c[0] + 40.0 * side, c[1] + 30.0, c[2] - 60.0], "radius": 0.01,
+                              "color": _mat([0.5, 0.5, 0.5])}}
+            return {"union": [bare(col), far]}
+
+        red, green, blue, yellow = [1.0, 0.1, 0.1], [0.1, 1.0, 0.1], [0.1, 0.1, 1.0], [1.0, 1.0, 0.1]
+        kind = FOREST_TIE_KINDS[k % 5]
+        pair = {"tr/rot": lambda: [_tr([0, 0, 0], bare(red)), _rot(0, k % 3, bare(green))],
+                "rot/sc": lambda: [_rot(0, k % 3, bare(green)), _sc([1, 1, 1], bare(blue))],
+                "sc/tr": lambda: [_sc([1, 1, 1], bare(blue)), _tr([0, 0, 0], bare(yellow))],
+                "rot/tr_union": lambda: [_rot(0, k % 3, bare(red)), _tr([0, 0, 0], wrapped(blue, -1))],
+                "tr_union/tr": lambda: [_tr([0, 0, 0], wrapped(yellow, 1)), _tr([0, 0, 0], bare(blue))]}[kind]()
+        if ((k // 5) % 2 == 1) != (kind in reverse):
+            pair = pair[::-1]
+        objs += pair
+    return _base(objs, recursion=2, dpi=dpi, lights=copy.deepcopy(_FOREST_LIGHTS[:2]))
+
+
+def forest_cases(dpi: int = 12) -> dict[str, dict]:
+    """The named forest scenes, each the smallest that reaches its edge of the
+    wave list (64 objects a chunk, 64 chunks a round of the device's chunk
+    tests, a list only above 256 objects) or of the ray tree:
+      mixed320    320 objects, one floor: six full chunks, no partial one
+      partial330  330 objects, three floors: a partial last chunk, three
+                  leading unbounded objects
+      floors70    400 objects, 70 floors: two unbounded chunks
+      bare257     257 objects, no unbounded one: the first chunk is all balls
+      rounds8300  8300 objects, one floor, at two thirds of dpi (32 x 24 at
+                  dpi 12): 131 chunks, three rounds of every chunk test
+      eager301    299 objects, a floor and one eager object: no list, the
+                  general kernels over 301 objects
+      form_ties   forest_tie_scene
+      concentric, collinear, far_clusters, giant_floor, nonfinite_bounds,
+      zero_scale  300 small spheres over a floor, arranged as the name says or
+                  standing beside such objects: one centre; one line; two
+                  clusters 1e6 apart; a radius-1e6 sphere as floor; spheres
+                  whose bounds overflow float (the centre, or only its
+                  square) and an image that overflows double (a sphere whose
+                  own bound overflows double answers every ray with a NaN hit
+                  in the reference: no scene to compare on); Scalings by 0
+                  and 1e-6 (never-hit objects and ones without a bound)
+      seed/<s>    s in FOREST_SEEDS: forest_scene(s, n, u) with n drawn from
+                  257..700 and u from {0, 1, 3}
+    mixed320+sun is mixed320 with FOREST_SUN attached (forest_load)."""
+    import random
+    out = {"mixed320": forest_scene(11, 320, 1, dpi=dpi), "partial330": forest_scene(12, 330, 3, dpi=dpi),
+           "floors70": forest_scene(13, 400, 70, dpi=dpi), "bare257": forest_scene(14, 257, 0, dpi=dpi),
+           "rounds8300": forest_scene(15, 8300, 1, dpi=max(1, dpi * 2 // 3)),
+           "eager301": forest_scene(16, 299, 1, eager=True, dpi=dpi), "form_ties": forest_tie_scene(dpi)}
+    out["mixed320+sun"] = out["mixed320"]
+    rnd = random.Random(17)
+    floor = _half([0, -1.4, 0], [0, 1, 0], _mat([0.6, 0.6, 0.6]))
+
+    def col(k):
+        return _mat([(k % 7) / 7.0, (k % 5) / 5.0, (k % 3) / 3.0], shininess=8 + 4 * (k % 5))
+
+    def small(k, p):
+        return _sph(p, 0.05 + 0.02 * (k % 4), col(k))
+
+    def cloud(k):
+        return small(k, [rnd.uniform(-3.4, 3.4), rnd.uniform(-1.1, 1.4), rnd.uniform(-7.5, -1.5)])
+
+    deg = {}
+    deg["concentric"] = [floor] + [_sph([0.0, 0.2, -3.0], 0.9 - 0.002 * k, col(k)) for k in range(300)]
+    deg["collinear"] = [floor] + [small(k, [-3.3 + 0.022 * k, -1.0 + 0.007 * k, -1.5 - 0.018 * k]) for k in range(300)]
+    deg["far_clusters"] = [floor] + [cloud(k) for k in range(150)] + \
+        [small(k, [1e6 + rnd.uniform(-3, 3), rnd.uniform(-1, 1), rnd.uniform(-7, -1)]) for k in range(150)]
+    deg["giant_floor"] = [_sph([0.0, -1e6 - 1.4, 0.0], 1e6, _mat([0.6, 0.6, 0.6]))] + [cloud(k) for k in range(300)]
+    deg["nonfinite_bounds"] = [floor] + [cloud(k) for k in range(300)] + [
+        _sph([1e39, 2e39, -1e39], 1e38, col(1)),                      # no float holds the centre
+        _sph([3e19, 1e19, -5e19], 1e19, col(2)),                      # ... nor its square
+        _tr([2e38, 2e38, 0], _sph([2e38, 2e38, -3.0], 1e30, col(3))),   # the image's centre, not the subject's
+        # an image beyond double: a Scaling by 1e6 or more carries no bound, the chain joins the unbounded lead
+        _sc([1e200, 1e200, 1e200], _sph([1e150, 1e150, 0], 1e100, col(4)))]
+    deg["zero_scale"] = [floor] + [cloud(k) for k in range(300)] + [
+        _sc([0, 0, 0], small(1, [0.0, 0.5, -2.0])), _sc([1, 0, 1], small(2, [0.5, 0.5, -2.0])),
+        _sc([1e-6, 1, 1], _sph([1e5, 0.3, -2.0], 0.5, col(3))),
+        _sc([1e-6, 1e-6, 1e-6], _sph([-5e5, 4e5, -2.5e6], 3e5, col(4))),
+        _tr([0.3, 0, 0], _sc([1, 1e-6, 1], _sph([0.0, 2e5, -3.0], 0.4, col(5))))]
+    for name, objs in deg.items():
+        out[name] = _base(objs, recursion=2, dpi=dpi, lights=copy.deepcopy(_FOREST_LIGHTS))
+    for s in FOREST_SEEDS:
+        rnd_s = random.Random(1000 + s)
+        out[f"seed/{s}"] = forest_scene(s, rnd_s.randint(257, 700), rnd_s.choice([0, 1, 3]), dpi=dpi)
+    return out
+
+
+FOREST_TREELESS = ("eager301",)
+
+
+def forest_load(rt, name: str, scene: dict):
+    """forest_cases()[name] as a loaded scene: mixed320+sun gets its directional light (rt = the rtamd module)."""
+    sc = rt.load_scene_from_json_text(json.dumps(scene))
+    return rt.with_dir_lights(sc, [FOREST_SUN]) if name.endswith("+sun") else sc
+
+
 # --------------------------------------------------- leaf-parameter scenes
 # Edge values of the leaf primitives' own parameters; the reference's loader
 # checks none of them (json_loader.cpp:211-297).

@@ -37,8 +37,11 @@ turned into IR by our loader (librt_host.so).  Outputs are data only:
                scenes.leaf_scene at LEAF_SEEDS), both modes, at LEAF_DPI, and
                Scene::intersect / Scene::occluded of the non-finite and
                overflowing ray groups (scenes.odd_ray_groups)
+  forest.npz   frames + counts of the forest scenes (scenes.forest_cases: more
+               than 256 objects of mixed forms), both modes, and
+               Scene::intersect / Scene::occluded of each case's query rays
 
-Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh shading graph leaves]
+Usage: python tests/golden/make_golden.py [frames kats jitter cameras dirlights deep crowd bvh shading graph leaves forest]
 """
 from __future__ import annotations
 
@@ -404,6 +407,34 @@ def make_leaves():
     print("leaf_rays:", len(data))
 
 
+def make_forest():
+    """The forest scenes (scenes.forest_cases at tests/test_forest_scenes.DPI),
+    both modes, and the reference's Scene::intersect / Scene::occluded of each
+    case's 768 query rays (the recipe of tests/test_forest_scenes.forest_case):
+    packed hit and occluded flags, t (0 for a miss), material (-1) and the
+    SHA-256 of the flags and full records (test_forest_scenes.records_digest;
+    the records themselves, 55 KB a case, do not fit the file's 1 MB)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_forest_scenes as F
+    data = {"dpi": np.array(F.DPI, dtype=np.int64)}
+    for name in F.KEYS:
+        sc = F.load(rtamd, name)
+        for mode in (0, 1):
+            with quiet_stdout():
+                fb, ni, no = rtamd.ref_render(sc, sc.width, sc.height, mode)
+            data[f"{name}/{mode}/fb"] = fb
+            data[f"{name}/{mode}/counts"] = np.array([ni, no], dtype=np.int64)
+        c = F.forest_case(rtamd, name)
+        ok, rec = rtamd.ref_scene_intersect(sc, c.rays)
+        data[f"{name}/q/hit"] = np.packbits(ok)
+        data[f"{name}/q/occ"] = np.packbits(rtamd.ref_scene_occluded(sc, c.seg_rays))
+        data[f"{name}/q/t"] = np.where(ok, rec["t"], 0.0)
+        data[f"{name}/q/mat"] = np.where(ok, rec["mat"], -1).astype(np.int32)
+        data[f"{name}/q/sha"] = F.records_digest(ok, rec)
+    np.savez_compressed(os.path.join(HERE, "forest.npz"), **data)
+    print("forest:", len(data), os.path.getsize(os.path.join(HERE, "forest.npz")), "bytes")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         for what in sys.argv[1:]:
@@ -420,3 +451,4 @@ if __name__ == "__main__":
     make_shading()
     make_graph()
     make_leaves()
+    make_forest()

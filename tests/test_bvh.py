@@ -80,6 +80,14 @@ def test_wave_bvh_structure(rt, name):
     b = _bvh(rt, scene)
     if b["n"] == 0:   # (eager programs: no BVH)
         pytest.skip("scene compiles to eager programs")
+    check_wave_bvh(b)
+
+
+def check_wave_bvh(b, slack=1e-6):
+    """The structure of a wave list (_bvh's dict): membership, the unbounded
+    lead and its padding, the chunk balls around their members' f32 balls
+    (reach <= r (1 + slack), in float64 from the stored floats) and the
+    records' magnitude word.  Returns the tightest reach / r over the chunks."""
     # every object except group headers and never-hit ones, exactly once
     # (entries -1: never-hit padding)
     real = b["worig"][b["worig"] >= 0]
@@ -89,6 +97,7 @@ def test_wave_bvh_structure(rt, name):
     # unbounded objects (types 1, 3) first, padded (type 0) to a chunk
     # boundary, then the bounded ones (type 2)
     t = b["wtype"]
+    worst = 0.0
     assert set(t.tolist()) <= {0, 1, 2, 3}
     first_ball = int(np.argmax(t == 2))
     assert first_ball % CHUNK == 0
@@ -104,13 +113,17 @@ def test_wave_bvh_structure(rt, name):
         cc, rc = b["wchunk"][c, :3].astype(np.float64), float(b["wchunk"][c, 3])
         m = b["wctab"][mem, :4].astype(np.float64)
         reach = np.linalg.norm(m[:, :3] - cc, axis=1) + m[:, 3]
-        assert np.all(reach <= rc * (1 + 1e-6)), (c, float(reach.max()), rc)
+        # (a ball of infinite radius holds every member, whatever inf - inf makes of its reach)
+        assert rc == np.inf or np.all(reach <= rc * (1 + slack)), (c, float(reach.max()), rc)
+        if np.isfinite(rc) and rc > 0:
+            worst = max(worst, float(reach.max()) / rc)
     # ball records (objects and chunks) carry |x| + |y| + |z| + r in word 5,
     # rounded up, for the device tests' margins (rt_device.hpp record_touch)
     for rec, typ in ((b["wctab"], t), (b["wchunk"], b["ctype"])):
         balls = rec[typ == 2].astype(np.float64)
         mag = np.abs(balls[:, :3]).sum(axis=1) + balls[:, 3]
         assert np.all(balls[:, 5] >= mag) and np.all(balls[:, 5] <= mag * (1 + 1e-6))
+    return worst
 
 
 def test_small_scenes_have_no_bvh(rt):

@@ -82,11 +82,14 @@ def _subtree_ok(nodes, i, end):
 
 @pytest.mark.parametrize("name", TREE_SCENES)
 def test_tree_structure(rt, name):
-    sc = scene(rt, name)
+    check_tree(rt, scene(rt, name), _bvh(rt, scene_dict(name)), name)
+
+
+def check_tree(rt, sc, wave, name):
+    """The structure of sc's ray tree over its wave list `wave` (test_bvh._bvh of the same scene)."""
     nodes, lead, n_wave = rt.ray_bvh_nodes(sc)
     n = len(nodes)
     assert n > 0 and 0 <= lead < n_wave
-    wave = _bvh(rt, scene_dict(name))   # the wave list the tree lies over (tests/test_bvh.py)
     assert wave["n"] == n_wave
     wctab, ctype = wave["wctab"], wave["wtype"]
     # the lead is the unbounded part of the wave list (and its padding): no ball records there, only balls behind
@@ -185,11 +188,17 @@ def test_culls_are_conservative_against_the_oracle(rt, name, pl):
         pc = Case.__new__(Case)
         pc.scene, pc.rt, pc.olib, pc.desc = sc, rt, rt.oracle_lib(), sc.desc_ptr
         ref_hit, ref_rec = pc.oracle_intersect(rays)
+    check_culls(rt, sc, rays, segs, ref_hit, ref_rec, f"{name} {pl}")
+
+
+def check_culls(rt, sc, rays, segs, ref_hit, ref_rec, what):
+    """The walk of `rays` up to the oracle's own closest t (ref_hit, ref_rec)
+    and of the segments `segs`: every object it does not reach is an oracle miss."""
     assert ref_hit.sum() >= len(rays) // 4
-    for what, rr in (("closest", _closest_ranges(base, rays, ref_hit, ref_rec)), ("segment", segs)):
+    for kind, rr in (("closest", _closest_ranges(None, rays, ref_hit, ref_rec)), ("segment", segs)):
         reached, tests = rt.ray_bvh_walk(sc, rr["o"], rr["d"], rr["tmin"], rr["tmax"])
-        n_skip = _unreached_all_miss(rt, sc, rr, reached, f"{name} {pl} {what}")
-        print(f"  {name} {pl} {what}: {len(rr)} rays, reached {reached.sum(axis=1).mean():.1f} of {reached.shape[1]} "
+        n_skip = _unreached_all_miss(rt, sc, rr, reached, f"{what} {kind}")
+        print(f"  {what} {kind}: {len(rr)} rays, reached {reached.sum(axis=1).mean():.1f} of {reached.shape[1]} "
               f"objects and {tests.mean():.1f} node tests per ray; {n_skip} skipped pairs are oracle misses")
 
 
