@@ -285,7 +285,7 @@ struct THit {   // intersect-mode hit
 
 // Per-lane op counters (RT_FLAG_COUNT_OPS builds only).
 //
-// Diagnostic builds with -DRT_PHASE_PROF (tools/build_exp.sh, never the
+// Diagnostic builds with -DRT_PHASE_PROF (tools/build_variant.sh, never the
 // product library) give the uncounted variant wave-level phase timers:
 // pb(k)/pe(k) bracket a phase at points where the whole wave is converged,
 // and the accumulated shader-clock cycles of lane 0 land in rt_stats.ops[k]
@@ -1850,6 +1850,48 @@ __device__ __forceinline__ int chunk_objects(const DevScene& S, int base) {
     }
     return n;
 }
+// RT_OPC_CULLED for the objects of the chunk at base that the candidate mask
+// m leaves out (op-counting builds; counts: the lane queries).
+template <bool KA, class CT>
+__device__ __forceinline__ void count_chunk_culled(const DevScene& S, int base, int n_objs, uint64_t m, bool counts, CT& cnt) {
+    if constexpr (kCounting<CT>) {
+        if (counts) {
+            int skipped = 0;
+            for (int o = base; o < n_objs && o < base + 64; ++o) {
+                const int k = scene_again<KA>(S, o).objs[o].kind;
+                if (k != rtamd::OBJ_GROUP && k != rtamd::OBJ_NEVER && !((m >> (o - base)) & 1)) ++skipped;
+            }
+            cnt_add(cnt, RT_OPC_CULLED, skipped);
+        }
+    }
+}
+
+// A chunk's candidate mask: the ballot of lane j's test of object j where
+// the wave-level cull holds (wave) and every lane is active, else all nc
+// objects left from the chunk's base on.
+__device__ __forceinline__ uint64_t chunk_candidates(bool wave, bool pass, int nc) {
+    return (wave && exec_full()) ? __ballot(pass) : (nc >= 64 ? ~0ull : ((1ull << nc) - 1));
+}
+
+// The line bundle of the querying lanes (need), lane f's line as the axis:
+// the double cone LB that line_touch tests CSG leaf balls against.
+template <bool UO>
+__device__ __forceinline__ void line_bundle(Cone& LB, const FRay& fr, int f, bool need) {
+    const float lox = rdlane_f(fr.ox, f), loy = rdlane_f(fr.oy, f), loz = rdlane_f(fr.oz, f);
+    const float lax = rdlane_f(fr.dx, f), lay = rdlane_f(fr.dy, f), laz = rdlane_f(fr.dz, f);
+    const float dxo = fr.ox - lox, dyo = fr.oy - loy, dzo = fr.oz - loz;
+    const float do2 = need ? dxo * dxo + dyo * dyo + dzo * dzo : 0.0f;
+    const float dc = need ? __builtin_fmaxf(0.0f, 1.0f - __builtin_fmaf(fr.dx, lax, __builtin_fmaf(fr.dy, lay, fr.dz * laz)))
+                          : 0.0f;
+    const float lrho = uni<UO>(sqrt_cull(__uint_as_float(wave_max_u32(__float_as_uint(do2)))));
+    const float dcm = __uint_as_float(wave_max_u32(__float_as_uint(dc))) + 4e-6f;
+    const float lcth = uni<UO>(1.0f - dcm);
+    LB.oxy = f2(lox, loy), LB.axy = f2(lax, lay), LB.oz = loz, LB.az = laz;
+    LB.cth = lcth;
+    LB.sth = uni<UO>(sqrt_cull(__builtin_fmaxf(0.0f, 1.0f - lcth * lcth)) + 1e-6f);
+    LB.rho = lrho;
+    LB.m5 = uni<UO>(1e-5f * (__builtin_fabsf(lox) + __builtin_fabsf(loy) + __builtin_fabsf(loz) + lrho + 1.0f));
+}
 
 
 // ------------------------------------------------- capsule shadow culls
@@ -1933,9 +1975,6 @@ __device__ __forceinline__ bool record_touch(const float4 c0, const float4 c1, c
 template <bool EAGER, bool DEEP, bool UO, bool BV = false, bool LEAD = false, bool KA = false, class CT>
 __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real tmin, real tmax, bool need, bool wave_ok,
                                     CT& cnt, bool regular = true) {
-#if defined(RT_ABL) && RT_ABL == 1   // diagnostic ablation builds only (wrong images): no shadow queries
-    return false;
-#endif
     cnt.pb(PH_WAVE_SETUP);
     const FRay fr = to_fray(r0);
     DRay r = r0;           // the exact ray, formed on the first object evaluation (wave-uniform)
@@ -2033,21 +2072,9 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
                                : __float_as_int(c1.x) != 0);
         // (lane j tests object j only with the whole wave active; otherwise
         // every object of the chunk is a candidate)
-        m = (cap && exec_full()) ? __ballot(pass) : (nc >= 64 ? ~0ull : ((1ull << nc) - 1));
+        m = chunk_candidates(cap, pass, nc);
         cnt.pe(PH_WAVE_SETUP);
-#if defined(RT_ABL) && RT_ABL == 2   // diagnostic: setup + transposed test only
-        if (m != 12345) return false;
-#endif
-        if constexpr (kCounting<CT>) {
-            if (need) {
-                int skipped = 0;
-                for (int o = base; o < n_objs && o < base + 64; ++o) {
-                    const int k = scene_again<KA>(S, o).objs[o].kind;
-                    if (k != rtamd::OBJ_GROUP && k != rtamd::OBJ_NEVER && !((m >> (o - base)) & 1)) ++skipped;
-                }
-                cnt_add(cnt, RT_OPC_CULLED, skipped);
-            }
-        }
+        count_chunk_culled<KA>(S, base, n_objs, m, need, cnt);
         }
         while (m) {
             const int o = base + __builtin_ctzll(m);
@@ -2090,28 +2117,10 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
                     continue;
                 }
                 if (!lb_ready) {
-                    // line bundle of the querying lanes (lane f's line as the axis)
                     lb_ready = true;
-                    const float lox = rdlane_f(fr.ox, f), loy = rdlane_f(fr.oy, f), loz = rdlane_f(fr.oz, f);
-                    const float lax = rdlane_f(fr.dx, f), lay = rdlane_f(fr.dy, f), laz = rdlane_f(fr.dz, f);
-                    const float dxo = fr.ox - lox, dyo = fr.oy - loy, dzo = fr.oz - loz;
-                    const float do2 = need ? dxo * dxo + dyo * dyo + dzo * dzo : 0.0f;
-                    const float dc = need ? __builtin_fmaxf(0.0f, 1.0f - __builtin_fmaf(fr.dx, lax, __builtin_fmaf(fr.dy, lay, fr.dz * laz)))
-                                          : 0.0f;
-                    const float lrho = uni<UO>(sqrt_cull(__uint_as_float(wave_max_u32(__float_as_uint(do2)))));
-                    const float dcm = __uint_as_float(wave_max_u32(__float_as_uint(dc))) + 4e-6f;
-                    const float lcth = uni<UO>(1.0f - dcm);
-                    LB.oxy = f2(lox, loy), LB.axy = f2(lax, lay), LB.oz = loz, LB.az = laz;
-                    LB.cth = lcth;
-                    LB.sth = uni<UO>(sqrt_cull(__builtin_fmaxf(0.0f, 1.0f - lcth * lcth)) + 1e-6f);
-                    LB.rho = lrho;
-                    LB.m5 = uni<UO>(1e-5f * (__builtin_fabsf(lox) + __builtin_fabsf(loy) + __builtin_fabsf(loz) + lrho + 1.0f));
+                    line_bundle<UO>(LB, fr, f, need);
                 }
-#ifdef RT_NO_LEAF_MASK
-                use_mask = false;
-#else
                 use_mask = LB.cth > 0.0f;
-#endif
                 if (use_mask) {
                     const bool full = exec_full();
                     const uint64_t b = __ballot(in && line_touch(g, LB));
@@ -2126,9 +2135,6 @@ __device__ bool scene_occluded_capsule(const DevScene& S, const DRay& r0, real t
                 }
             }
             cnt.pe(PH_OBJ_PREF);
-#if defined(RT_ABL) && RT_ABL == 3   // diagnostic: everything but the shadow object evaluations
-            if (m != 12345) continue;
-#endif
             const bool csg_obj = ob.kind == rtamd::OBJ_CHAIN && ob.core != 0;
             if (csg_obj) cnt.pb(PH_SHADOW_CSG);
             cnt.pb(PH_OBJ_HIT);
@@ -2375,9 +2381,6 @@ __device__ __forceinline__ uint64_t sub_bundle_mask(const float4 c0, const float
 template <bool EAGER, bool DEEP, bool UO, bool BV = false, class CT>
 __device__ bool scene_occluded_wave(const DevScene& S, const DRay& r0, real tmin, real tmax, bool need, bool wave_ok,
                                     CT& cnt, int li, const ShadowHull& H, bool regular) {
-#if defined(RT_ABL) && RT_ABL == 1   // diagnostic ablation builds only (wrong images): no shadow queries
-    return false;
-#endif
     cnt.pb(PH_WAVE_SETUP);
     DRay r = r0;           // the exact ray, formed on the first object evaluation (wave-uniform)
     bool r_exact = false;
@@ -2455,7 +2458,7 @@ __device__ bool scene_occluded_wave(const DevScene& S, const DRay& r0, real tmin
         const bool pass = (j < S.n_objs) & (cone ? lrec_touch(c0, c1, K) : __float_as_int(c1.x) != 0);
         // (lane j tests object j only with the whole wave active; otherwise
         // every object of the chunk is a candidate)
-        uint64_t m = (cone && exec_full()) ? __ballot(pass) : (nc >= 64 ? ~0ull : ((1ull << nc) - 1));
+        uint64_t m = chunk_candidates(cone, pass, nc);
         // Sub-bundles: where the wave's hull lets many objects of a chunk
         // through (a tile straddling depth edges of an incoherent scene), each
         // object is tested again against the eight per-pixel hulls (a pixel's
@@ -2463,19 +2466,7 @@ __device__ bool scene_occluded_wave(const DevScene& S, const DRay& r0, real tmin
         if (cone && __builtin_popcountll(m) > kSubBundleMin && exec_full())
             m &= sub_bundle_mask(c0, c1, r0, tmin, need, nm, Lx, Ly, Lz);
         cnt.pe(PH_WAVE_SETUP);
-#if defined(RT_ABL) && RT_ABL == 2   // diagnostic: setup + transposed test only
-        if (m != 12345) return false;
-#endif
-        if constexpr (kCounting<CT>) {
-            if (need) {
-                int skipped = 0;
-                for (int o = base; o < S.n_objs && o < base + 64; ++o) {
-                    const int k = S.objs[o].kind;
-                    if (k != rtamd::OBJ_GROUP && k != rtamd::OBJ_NEVER && !((m >> (o - base)) & 1)) ++skipped;
-                }
-                cnt_add(cnt, RT_OPC_CULLED, skipped);
-            }
-        }
+        count_chunk_culled<false>(S, base, S.n_objs, m, need, cnt);
         while (m) {
             const int o = base + __builtin_ctzll(m);
             m &= m - 1;
@@ -2512,29 +2503,10 @@ __device__ bool scene_occluded_wave(const DevScene& S, const DRay& r0, real tmin
                     continue;
                 }
                 if (!lb_ready) {
-                    // line bundle of the querying lanes (lane f's line as the axis)
                     lb_ready = true;
-                    const FRay fr = to_fray(r0);
-                    const float lox = rdlane_f(fr.ox, f), loy = rdlane_f(fr.oy, f), loz = rdlane_f(fr.oz, f);
-                    const float lax = rdlane_f(fr.dx, f), lay = rdlane_f(fr.dy, f), laz = rdlane_f(fr.dz, f);
-                    const float dxo = fr.ox - lox, dyo = fr.oy - loy, dzo = fr.oz - loz;
-                    const float do2 = need ? dxo * dxo + dyo * dyo + dzo * dzo : 0.0f;
-                    const float dc = need ? __builtin_fmaxf(0.0f, 1.0f - __builtin_fmaf(fr.dx, lax, __builtin_fmaf(fr.dy, lay, fr.dz * laz)))
-                                          : 0.0f;
-                    const float lrho = uni<UO>(sqrt_cull(__uint_as_float(wave_max_u32(__float_as_uint(do2)))));
-                    const float dcm = __uint_as_float(wave_max_u32(__float_as_uint(dc))) + 4e-6f;
-                    const float lcth = uni<UO>(1.0f - dcm);
-                    LB.oxy = f2(lox, loy), LB.axy = f2(lax, lay), LB.oz = loz, LB.az = laz;
-                    LB.cth = lcth;
-                    LB.sth = uni<UO>(sqrt_cull(__builtin_fmaxf(0.0f, 1.0f - lcth * lcth)) + 1e-6f);
-                    LB.rho = lrho;
-                    LB.m5 = uni<UO>(1e-5f * (__builtin_fabsf(lox) + __builtin_fabsf(loy) + __builtin_fabsf(loz) + lrho + 1.0f));
+                    line_bundle<UO>(LB, to_fray(r0), f, need);
                 }
-#ifdef RT_NO_LEAF_MASK
-                use_mask = false;
-#else
                 use_mask = LB.cth > 0.0f;
-#endif
                 if (use_mask) {
                     const bool full = exec_full();
                     const uint64_t b = __ballot(in && line_touch(S.gb + 4 * k, LB));
@@ -2573,9 +2545,7 @@ __device__ bool scene_occluded_wave(const DevScene& S, const DRay& r0, real tmin
                 }
             }
             cnt.pe(PH_OBJ_PREF);
-#if defined(RT_ABL) && RT_ABL == 3   // diagnostic: everything but the shadow object evaluations
-            if (m != 12345) continue;
-#endif
+            // (from here to the loop's end: scene_occluded_capsule's evaluation tail, line for line; keep the two in step)
             const bool csg_obj = ob.kind == rtamd::OBJ_CHAIN && ob.core != 0;
             if (csg_obj) cnt.pb(PH_SHADOW_CSG);
             cnt.pb(PH_OBJ_HIT);
@@ -2739,16 +2709,9 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
         const bool pass = (j < n_objs) & (type != 0) &
                           ((type != 2) | wide | cone_touch(c0, c1.y, K));
         const int nc = n_objs - base;
-        m = (cone && exec_full()) ? __ballot(pass) : (nc >= 64 ? ~0ull : ((1ull << nc) - 1));
+        m = chunk_candidates(cone, pass, nc);
         cnt.pe(PH_WAVE_SETUP);
-        if constexpr (kCounting<CT>) {
-            int skipped = 0;
-            for (int o = base; o < n_objs && o < base + 64; ++o) {
-                const int k = scene_again<KA>(S, o).objs[o].kind;
-                if (k != rtamd::OBJ_GROUP && k != rtamd::OBJ_NEVER && !((m >> (o - base)) & 1)) ++skipped;
-            }
-            if (valid) cnt_add(cnt, RT_OPC_CULLED, skipped);
-        }
+        count_chunk_culled<KA>(S, base, n_objs, m, valid, cnt);
         }
         while (m) {
             const int o = base + __builtin_ctzll(m);
@@ -2760,16 +2723,7 @@ __device__ bool scene_intersect_wave(const DevScene& S, const DRay& r, real tmin
             // CSG objects: the bundle reaches no leaf ball (DevObj::pb0);
             // otherwise the leaves whose balls no lane's line meets
             uint64_t lmask = ~0ull;
-#ifdef RT_NO_LEAF_MASK
-            const bool use_mask = false;
-            if (kCsg<CT> && !wide && ob.npb > 0 && exec_full() && !__any(lane < ob.npb && cone_touch(S.gb + 4 * (ob.pb0 + (lane < ob.npb ? lane : 0)), K))) {
-                if (valid) cnt.inc(RT_OPC_CULLED);
-                cnt.pe(PH_OBJ_PREF);
-                continue;
-            }
-#else
             const bool use_mask = kCsg<CT> && !wide && ob.npb > 0 && exec_full();
-#endif
             if (use_mask) {
                 const float* g = scene_again<KA>(S, o).gb + 4 * (ob.pb0 + (lane < ob.npb ? lane : 0));
                 const bool in = lane < ob.npb;
@@ -3089,9 +3043,6 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
             cnt.pe(PH_SHADE1);
             cnt.pb(PH_SHADE2);
         }
-#if defined(RT_ABL) && RT_ABL == 4   // diagnostic: no pass-2 accumulation
-        if (lit != 12345u) continue;
-#endif
         if (!lit) continue;
         const MatT* m = &scene_again<KA>(S, l0).mats[hit.mat];
         const real kd = m->kd, ks = m->ks, shin = m->shininess;
@@ -3169,7 +3120,9 @@ __device__ V3 shade(const DevScene& S, real ht, const DHit& hit, V3 wo, uint32_t
 // r.d.normalized() of the traced Ray; n and p are the hit's as stored.  They
 // are functions of values only: the two choices by front_face (eta, and which
 // child starts on which side) stay selects at the call sites, where they always
-// were - moved into a helper they changed the frame kernels' code.
+// were - moved into a helper they changed the frame kernels' code.  So did
+// the whole refraction block of trace_wave() and trace() as one function, in
+// four forms (profiles/wave_query_helpers/forms_tried.txt): it stays twice.
 // reflect(incident, n).normalized() (tracer.cpp:41, 76-78)
 __device__ __forceinline__ V3 reflect_dir(V3 inc, V3 n) {
     const real k = RV(2.0) * dot3(inc, n);
@@ -3392,9 +3345,7 @@ __device__ __forceinline__ V3 trace_wave(const DevScene& S, DRay r0, uint32_t& n
 // Tracer::trace_recursive (tracer.cpp:22-73) as an explicit frame stack.
 template <bool EAGER, bool DEEP, bool SECONDARY, bool DL, int WV, bool KA = false, class CT>
 __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect, uint32_t& n_occl, CT& cnt) {
-#ifndef RT_OLD_TRACE
     if constexpr (SECONDARY && WV) return trace_wave<EAGER, DEEP, DL, WV>(S, r, n_isect, n_occl, cnt);
-#endif
     if constexpr (!SECONDARY) {
         // No material reflects or refracts (or recursion <= 1): trace_recursive
         // reduces to one closest hit + local shading (tracer.cpp:22-37, 72).
@@ -3411,9 +3362,6 @@ __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect
                                                                __builtin_amdgcn_read_exec() == ~0ull, cnt);
             cnt.pe(PH_PRIMARY);
             if (!__any(hit)) return background(S);
-#if defined(RT_ABL) && RT_ABL == 5   // diagnostic: primary hit only, no shading
-            if (S.n_objs != 12345) return hit ? h.n : background(S);
-#endif
             const V3 E = shade<EAGER, DEEP, DL, WV, RT_STD_UO, false, KA>(S, ht, h, normalized(vneg(r.d)), n_occl, cnt, hit);
             return hit ? E : background(S);
         } else {
@@ -3446,6 +3394,7 @@ __device__ __forceinline__ V3 trace(const DevScene& S, DRay r, uint32_t& n_isect
                     const MatT* mat = &S.mats[h.mat];
                     const bool can = depth < limit - 1;
                     const bool want_refl = mat->kr > RV(0.0) && can;
+                    // (the refraction child: trace_wave's block, line for line; keep the two in step)
                     bool want_refr = false;
                     DRay refr;
                     if (mat->kt > RV(0.0) && can) {

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Wave-level event counts of the standard-mode trace kernel (diagnostic).
 
-Needs a library built with -DRT_EVENT_PROF (tools/build_exp.sh ev
-"-DRT_EVENT_PROF"), loaded with RTAMD_LIB=...; rt_stats.ops[k] then counts
+Needs a library built with -DRT_EVENT_PROF (tools/build_variant.sh ev
+-DRT_EVENT_PROF), loaded with RTAMD_LIB=...; rt_stats.ops[k] then counts
 how many times a wave executed event k (EV_* in rt_device.hpp).  Prints the
 counts per wave.  Usage (GPU box): RTAMD_LIB=... python tools/event_prof.py [config]"""
 import ctypes as C

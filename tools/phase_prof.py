@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Phase breakdown of the standard-mode trace kernel (diagnostic).
 
-Needs a library built with -DRT_PHASE_PROF (tools/build_exp.sh prof
-"-DRT_PHASE_PROF"), loaded with RTAMD_LIB=...; rt_stats.ops[k] then holds the
+Needs a library built with -DRT_PHASE_PROF (tools/build_variant.sh prof
+-DRT_PHASE_PROF), loaded with RTAMD_LIB=...; rt_stats.ops[k] then holds the
 shader-clock cycles lane 0 of every full wave spent in phase k (PH_* in
 rt_device.hpp).  Prints each phase's share of the summed wave time.
 Usage (GPU box): RTAMD_LIB=.../librtamd_prof.so python tools/phase_prof.py [config]"""
