@@ -300,7 +300,7 @@ int rt_test_pokeball_thresholds(double btn_outer, double ring_width, double* out
  * bit 3 halved at the frame border, bit 4 the hatch bit (white). */
 double rt_test_paper_code_value(int code);
 /* CPU: the frame planners of csrc/host/frame_plan.hpp, the host-only code
- * rt_render.hip and rt_dist.hip execute.  All return an rt_status.
+ * rt_frame.hip and rt_dist.hip execute.  All return an rt_status.
  *
  * rt_test_plan_dist: rank's part of an H-row frame over `world` ranks
  * (plan_dist_frame; kind 0 = FP64 output, the root sheds strips by mode,

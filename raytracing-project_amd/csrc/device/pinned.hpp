@@ -74,7 +74,7 @@ hipError_t host_copy_async(void* dst, const void* src_pinned, size_t n, hipStrea
 // st, so that the runtime's one-time set-up of that path (~8 ms of host time
 // in the call, profiles/r06d_first_op.txt) runs while the frame's first trace
 // executes instead of in front of the frame's read-back.
-hipError_t warm_copy_engine(hipStream_t st);
+hipError_t warm_copy_engine(hipStream_t st);   // (rt_frame.hip)
 
 // H2D through the arena: page-locked staging + k_host_copy (pageable
 // hipMemcpyAsync if the arena has no room).

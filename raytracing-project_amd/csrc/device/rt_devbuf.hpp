@@ -1,5 +1,5 @@
 // rt_devbuf.hpp — the growable device buffer and the HIP error macro shared
-// by the host sides of librtamd (rt_render.hip, rt_dist.hip, rt_test_hooks.hip).
+// by the host sides of librtamd (rt_workspace.hpp, rt_render.hip, rt_dist.hip, rt_test_hooks.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -6,7 +6,7 @@
 // geometry rows).  The partition, its chunks and the root's placement table
 // are host-only code (csrc/host/frame_plan.hpp plan_dist_frame); this file
 // executes that plan.  Every rank runs
-// the ordinary trace (rt_frame_* of rt_render.hip) on its rows, chunk by
+// the ordinary trace (rt_frame_* of rt_frame.hip) on its rows, chunk by
 // chunk, and each chunk is handed to ONE RCCL collective, ncclGather to rank
 // 0 over xGMI, on a high-priority stream so it overlaps the tracing of the
 // next chunk; rank 0 places the gathered strips into its frame.  Paper-mode

@@ -1,6 +1,6 @@
 // rt_kernels.hpp — the render kernels, built once per precision right after
-// rt_device.hpp (RT_NS = rtd: FP64 parity path, rt_render.hip; RT_NS = rtf:
-// FP32 fast path, rt_render_f32.hip).
+// rt_device.hpp (RT_NS = rtd: FP64 parity path, rt_kernels_f64.hip; RT_NS = rtf:
+// FP32 fast path, rt_kernels_f32.hip).
 //
 // Standard mode (Tracer::render, tracer.cpp:282-300):
 //   k_std: one lane per (pixel, sample); a wave covers 4x2 pixels x 8 samples,
@@ -291,7 +291,7 @@ __device__ __forceinline__ int paper_tile_y() {
     return kPaperWPB == 4 ? (int)blockIdx.y * 2 + (int)(threadIdx.x >> 7) : (int)blockIdx.y;
 }
 // A primary wave's (start, end) tick slot: group-major, one per 8-column tile
-// (2 * ceil(W / 16) of them, rt_render.hip paper_waves_per_group) per 8-entry
+// (2 * ceil(W / 16) of them, frame_plan.hpp paper_waves_per_group) per 8-entry
 // list group.
 __device__ __forceinline__ unsigned* paper_wave_slot(const PaperParams& P) {
     const unsigned g = __builtin_amdgcn_readfirstlane(paper_tile_y()), xt = __builtin_amdgcn_readfirstlane(paper_tile_x());
@@ -629,7 +629,7 @@ const KernelRow<DevScene, PaperParams> kPaperKernels[] = {
 #undef RT_ROW
 
 // The finish kernels by (CODES, PAIR).  RT_NO_PAPER_CODES (the FP32 build)
-// drops the CODES rows: paper codes need an FP64 frame (rt_render.hip
+// drops the CODES rows: paper codes need an FP64 frame (rt_frame.hip
 // frame_trace refuses them with RT_FLAG_FP32, and rt_dist.hip gathers doubles
 // from FP32 ranks), so no frame can ask this namespace for them.
 constexpr unsigned fkey(bool codes, bool pair) { return (unsigned)codes | (unsigned)pair << 1; }

@@ -2,11 +2,11 @@
 // nothing of a frame's state: the jitter-stream checks, the scene compiler's
 // reports, the kernel a frame would launch (pick_variant + the dispatch
 // tables), the tables' rows, the launch log the launchers fill
-// (rtamd::note_launch), the frame planners of csrc/host/frame_plan.hpp and the
-// jitter cache's logic over host memory (csrc/host/jitter_cache.hpp).  (The
-// distributed-frame hooks live with their transport in rt_dist.hip, rt_test_div3
-// and rt_test_norm3 with the FP64 kernels, the jitter cache's counts and budget with the
-// workspaces in rt_render.hip.)
+// (rtamd::note_launch), the frame planners of csrc/host/frame_plan.hpp, the
+// jitter cache's logic over host memory (csrc/host/jitter_cache.hpp) and its
+// counts and budget in the workspaces, and the batched calls' chunk sizes
+// (rt_workspace.hpp).  (The distributed-frame hooks live with their transport
+// in rt_dist.hip, rt_test_div3 and rt_test_norm3 with the FP64 kernels.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,10 +26,11 @@
 #include "rt_internal.hpp"
 #include "rt_launch.hpp"
 #include "rt_test.h"
+#include "rt_workspace.hpp"
 #include "scene_compile.hpp"
 
 namespace {
-using DBuf = rtamd::DevBufT<8>;
+using rtw::DBuf;
 
 using rtamd::KernelNamespace;
 using rtamd::KernelVariant;
@@ -521,11 +522,7 @@ extern "C" int rt_test_jitter_cache_sim(const int64_t* ops, int n_ops, int64_t b
 
 namespace {
 bool rows_ok(int H, const int32_t* rows, int n_rows) {
-    if (H <= 0 || n_rows <= 0 || n_rows > H || !rows) return false;
-    std::vector<char> seen(H, 0);
-    for (int i = 0; i < n_rows; ++i)
-        if (rows[i] < 0 || rows[i] >= H || seen[rows[i]]++) return false;
-    return true;
+    return H > 0 && n_rows > 0 && n_rows <= H && rows && rtw::check_rows(nullptr, H, rows, n_rows) == RT_OK;
 }
 }  // namespace
 
@@ -590,5 +587,51 @@ extern "C" int rt_test_plan_paper_calls(int W, int H, const int32_t* rows, int n
         if (c.ok && k == rollback_after) pc.rollback();
     }
     std::copy(pc.ext_done().begin(), pc.ext_done().end(), ext_done_out);
+    return RT_OK;
+}
+
+// ------------------------------------------- workspaces (rt_workspace.hpp)
+// The jitter cache of workspace (current device, slot).  Takes the workspace
+// lock: not for a thread that holds an open frame of that workspace.
+extern "C" int rt_test_jitter_cache_stats_slot(int slot, uint64_t* hits, uint64_t* misses, uint64_t* entries,
+                                               uint64_t* bytes) {
+    if (!hits || !misses || !entries || !bytes) return RT_ERR_INVALID_ARG;
+    *hits = *misses = *entries = *bytes = 0;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    rtw::Workspace* w = rtw::find_workspace(dev, slot);
+    if (!w) return RT_OK;   // (no frame of that slot yet)
+    std::lock_guard<std::mutex> wl(w->mu);
+    const rtamd::JitterCache& jc = w->frame.jcache;
+    *hits = jc.hits();
+    *misses = jc.misses();
+    *entries = jc.entries();
+    *bytes = jc.bytes();
+    return RT_OK;
+}
+
+extern "C" int rt_test_jitter_cache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries, uint64_t* bytes) {
+    return rt_test_jitter_cache_stats_slot(rtw::workspace_slot(), hits, misses, entries, bytes);
+}
+
+extern "C" int rt_test_jitter_cache_budget(int64_t bytes) {
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    rtamd::set_jitter_cache_budget(bytes);
+    rtw::each_workspace(INT32_MIN, [](rtw::Workspace& w) {
+        w.frame.jcache.clear();
+        w.frame.jcache.reset_counts();
+    });
+    (void)hipSetDevice(prev);
+    return RT_OK;
+}
+
+extern "C" int rt_test_camera_chunk_rays(size_t n) {
+    rtw::g_chunk_items.store(n ? n : rtw::kChunkItems);
+    return RT_OK;
+}
+
+extern "C" int rt_test_scatter_launch_items(size_t n) {
+    rtw::g_scatter_items.store(n ? std::min(n, rtw::kLaunchItems) : rtw::kLaunchItems);
     return RT_OK;
 }

@@ -4,7 +4,7 @@
 // how they are chunked and where a gathered slot lands (plan_dist_frame), the
 // standard-mode jitter layout (plan_std_frame) and the paper-mode halo rows,
 // buffer layout and per-call lists (plan_paper_frame, PaperCalls).
-// rt_render.hip and rt_dist.hip execute these plans; tests/test_frame_plan.py
+// rt_frame.hip and rt_dist.hip execute these plans; tests/test_frame_plan.py
 // checks them on the CPU through the rt_test_plan_* hooks and
 // tools/sanitize/host_check.cpp runs them under ASan/UBSan.
 #pragma once
@@ -54,7 +54,7 @@ struct KernelVariant {
 const char* variant_ns_name(int ns);   // "rtd" / "rtf" / "rtdb"
 
 // The variant a frame of (scene, mode, flags) launches.  bvh_enabled: false
-// when the frame's BVH trial (rt_render.hip SceneCache) runs it without the
+// when the frame's BVH trial (rt_workspace.hpp SceneCache) runs it without the
 // wave BVH.  RT_OK, or RT_ERR_UNSUPPORTED with the message set: a scene
 // beyond the big stacks, or beyond the common ones in FP32.
 int pick_variant(const CompiledScene& cs, const rt_scene_desc& d, int mode, int flags, bool bvh_enabled,

@@ -12,7 +12,7 @@
 //
 // One buffer per entry: [the draws, 16 doubles per pixel | rows_jrow].  The
 // cache decides hit / miss / eviction and calls back for device memory; the
-// caller (rt_render.hip frame_begin / frame_end) enqueues the upload and the
+// caller (rt_frame.hip frame_begin / frame_end) enqueues the upload and the
 // fill and reports the frame's completion.  Not thread-safe: used under the
 // workspace lock, which a frame holds from begin to end, so at most one frame
 // of a cache is open and its entry cannot be evicted (evictions happen in

@@ -186,7 +186,7 @@ NodeProgram compile_node_program(const rt_scene_desc& d, int node, int kind);
 // and the device compares x with these two thresholds instead of evaluating
 // acos: the reference's decision exactly (the device math library's acos
 // could differ from glibc's in the last bit).  No such x: xb = 2 / xi = -2.
-// Device node slots of a pokeball (rt_render.hip frame_begin fills them in
+// Device node slots of a pokeball (rt_workspace.hip scene_resident fills them in
 // the device copy of the nodes; the IR's v[10..23] of a pokeball are unused).
 constexpr int kPokeXb = 20, kPokeXi = 21;
 void pokeball_thresholds(double btn_outer, double ring_width, double& xb, double& xi);

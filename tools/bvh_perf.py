@@ -34,7 +34,7 @@ def run(name, scene, mode=0, reps=3):
     (_, tb, rays), (_, tn, rays_n) = out
     assert rays == rays_n
     # the product's default: the first two frames of a shape try the BVH and
-    # the flat list, later frames take the faster (rt_render.hip SceneCache);
+    # the flat list, later frames take the faster (rt_workspace.hpp SceneCache);
     # a fresh scene handle starts the trial over
     sc2 = rtamd.load_scene_from_json_text(json.dumps(scene))
     st = rtamd.Stats()

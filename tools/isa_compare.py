@@ -26,6 +26,8 @@ The rule it holds the pair to:
   * op-counting functions (C = true, Cnt<true>; launched under
     RT_FLAG_COUNT_OPS only): may move; each one that did is listed with its
     instruction count before and after and its metadata.
+  * an object that only one build has (objects pair by file name) breaks the
+    rule only if it holds device functions; a host-only one is noted.
 
 Exit status 0 if the rule holds, 1 if not.  --strict holds the op-counting
 functions to the first rule too.
@@ -169,8 +171,13 @@ def main():
         for name in names:
             po, no = os.path.join(a.parent, name), os.path.join(a.new, name)
             if not (os.path.exists(po) and os.path.exists(no)):
-                print(f"{name}: only in the {'parent' if os.path.exists(po) else 'new'} build")
-                broken.append(f"{name}: object missing from one build")
+                # an object of one build only breaks the rule only if it holds device functions
+                side, only, tmp = ("parent", po, tp) if os.path.exists(po) else ("new", no, tn)
+                co = code_object(only, tmp)
+                n_fn = len(functions(co)) if co else 0
+                print(f"{name}: only in the {side} build, " + (f"with {n_fn} device functions" if n_fn else "no device code"))
+                if n_fn:
+                    broken.append(f"{name}: an object with device functions is missing from one build")
                 continue
             pc, nc = code_object(po, tp), code_object(no, tn)
             if pc is None and nc is None:
